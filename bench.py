@@ -5,7 +5,12 @@ One "step" = one pass of the hot path over one batch: encoder -> clip|reparam|KL
 i.e. getEval(missing_prob=0) (reference nolbo.py:1463-1501), inputs resident in HBM.  Workload = BASELINE.json
 configs[1] (ModelNet40 VAE, 32^3, batch 256, bf16); synthetic voxels + random-init weights (no dataset/weights exist).
 
-    python bench.py --gpus N --steps K --warmup W [--dtype bf16|f32|fp8] [--mode eval|train] [--streams S]
+    python bench.py --gpus N --steps K --warmup W [--dtype bf16|f32|fp8] [--mode eval|train] [--streams S] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `global_metrics` of the last
+timed step, `whole_path` from the shapes).  Everything else -- the per-layer breakdown, the one-stream rate, the per-kernel roofline,
+the CPU baselines, the parity legs, the host-array legs, config1_b4 and, in training, the all-reduce overlap report -- runs only with
+--full; without it those fields of the line are null.  --dump-outputs DIR writes what the last timed step returned (see dump_outputs).
 
 Scheduling: by default the K steps (independent batches, as in the reference's test loop test_modelnet_VAE.py:114-130) are
 issued round-robin on 3 HIP streams over ONE model (voxvae/streams.py; the engines keep a workspace per stream): the latency-bound
@@ -21,7 +26,7 @@ fewer than N GPUs are visible.  Under torch.distributed.run (RANK set) it is a r
 r runs its own 256 reconstructions (weak scaling), no data-path collective; the 8 metric scalars of SURVEY.md §8(e) are
 summed once by an RCCL all-reduce after the timed region (reference DP semantics: AE3D.py:92-104).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+Prints ONE JSON line (rank 0) with the driver's contract fields plus, with --full,
   roofline       dominant kernel, HIP events on the launch stream inside the timed region; `traffic` only from a PMC summary
                  stamped with the current kernel sources (profiles/summarize.py stamp), else null + traffic_stale
   cpu_baseline   the fp32 C oracle on the host cores (rank 0 at N = 1 only, bounded sample) + a torch-CPU bracket
@@ -74,7 +79,36 @@ def parse(argv=None):
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'], help="process-group backend ('nccl' = RCCL; 'gloo' with --dry-run only)")
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher / collective rehearsal without a GPU: ranks fabricate per-rank metrics and run the same reduction code')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every secondary leg (per-layer breakdown, one-stream rate, roofline, CPU baselines, parity, host-array legs, '
+                         'config1_b4; in training the all-reduce overlap, roofline and CPU legs); off: only the headline figure')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all; rank 0)')
     return ap.parse_args(argv)
+
+
+DUMP_BYTES = 63 * 10 ** 6          # --dump-outputs: 64 MB in all, .npy headers included
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: `arrays` (name -> tensor, in order) as DIR/<name>.npy, float64 and integer tensors as float64, everything
+    else as float32.  Inputs
+    are seeded, so two builds run with the same arguments can be compared array for array.  When the arrays exceed DUMP_BYTES, an
+    array larger than its share of what is left is replaced by a fixed sample of its elements (numpy seed 0, ascending flat index):
+    at 32^3 / batch 256 nothing is sampled."""
+    os.makedirs(dirname, exist_ok=True)
+    host = [(n, t.detach().double().cpu().numpy() if t.dtype in (torch.float64, torch.int64, torch.int32)
+             else t.detach().float().cpu().numpy()) for n, t in arrays if t is not None]
+    left, order = DUMP_BYTES, sorted(range(len(host)), key=lambda i: host[i][1].nbytes)
+    for k, i in enumerate(order):
+        name, v = host[i]
+        share = left // (len(order) - k)
+        if v.nbytes > share:
+            flat = v.reshape(-1)
+            keep = np.sort(np.random.default_rng(0).choice(flat.size, share // v.itemsize, replace=False))
+            v = flat[keep]
+        np.save(os.path.join(dirname, name + '.npy'), v)
+        left -= v.nbytes
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -294,10 +328,11 @@ def bench_train(a, model, x, eps, world, rank, dev, dist, cfg=None, ep=None, dp=
     # wgrad_phase_kernel<3> + the reduce of its slabs = one vv_wgrad_conv_k4s2 call, twice per step); HIP events on the launch stream
     fe = model._enc_eng.filters
     dom = 'wgrad:%d:%d:%d' % (a.voxel // 2, fe[0], fe[1])
-    tr.timer = E.LayerTimer(only=dom)
+    tr.timer = E.LayerTimer(only=dom) if a.full else None
     for _ in range(a.warmup):
         tr.step(x, x, eps)
-    tr.timer.events.clear()
+    if tr.timer is not None:
+        tr.timer.events.clear()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
@@ -309,6 +344,17 @@ def bench_train(a, model, x, eps, world, rank, dev, dist, cfg=None, ep=None, dp=
         dist.barrier()
     el = time.perf_counter() - t0
     sums, el, nranks = reduce_metrics(dist, metric_vector(stats, kl), el, dev)
+    if a.dump_outputs and rank == 0:
+        # what fit() hands back: the step's losses / counts, and the weights Adam has just moved (one flat vector per model)
+        weights = [(n, torch.cat([p.reshape(-1).float() for _, p in sorted(eng.params.items())]))
+                   for n, eng in (('weights_encoder', model._enc_eng), ('weights_decoder', model._dec_eng))]
+        dump_outputs(a.dump_outputs, [('kl', kl), ('stats', stats), ('metrics', metrics)] + weights)
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(train_line(a, world, el, nranks, dist, sums, metrics, kl, None, None, None)))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # how much of the gradient all-reduce hides under the backward pass: exposed = what finish() still waits for after the last
     # backward kernel (events on the launch stream, 10 extra steps outside the timed region), total = the same buckets
     # all-reduced back to back on an otherwise idle device
@@ -355,18 +401,22 @@ def bench_train(a, model, x, eps, world, rank, dev, dist, cfg=None, ep=None, dp=
     if rank == 0 and world == 1 and a.cpu_samples > 0 and cfg is not None:
         cpu = train_cpu_baseline(cfg, ep, dp, xh, epsh)
     if rank == 0:
-        print(json.dumps({'metric': '32^3 voxel VAE training samples/sec (fit: fwd + bwd + Adam)', 'value': world * a.batch * a.steps / el,
-                          'unit': 'samples/s', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': 1e3 * el / a.steps,
-                          'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': a.dtype, 'data': 'synthetic',
-                          'config': {'workload': 'ModelNet40 VAE fit(), %d^3 voxels, latent %d, batch %d per GPU (BASELINE.json configs[3])'
-                                                 % (a.voxel, a.latent, a.batch), 'global_batch': a.batch * world,
-                                     'parallelism': 'dp%d, bucketed RCCL all-reduce of gradients, per-rank BatchNorm' % world},
-                          'rccl_world_size': nranks, 'process_group': dist.get_backend() if dist is not None else None,
-                          'global_metrics': global_metrics(sums), 'gradient_all_reduce': overlap,
-                          'roofline': roof, 'cpu_baseline': cpu,
-                          'final_loss_shape': float(metrics[0]), 'final_loss_kl': float(kl.mean())}))
+        print(json.dumps(train_line(a, world, el, nranks, dist, sums, metrics, kl, overlap, roof, cpu)))
     if dist is not None:
         dist.destroy_process_group()
+
+
+def train_line(a, world, el, nranks, dist, sums, metrics, kl, overlap, roof, cpu):
+    return {'metric': '32^3 voxel VAE training samples/sec (fit: fwd + bwd + Adam)', 'value': world * a.batch * a.steps / el,
+            'unit': 'samples/s', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': 1e3 * el / a.steps,
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': a.dtype, 'data': 'synthetic', 'full': a.full,
+            'config': {'workload': 'ModelNet40 VAE fit(), %d^3 voxels, latent %d, batch %d per GPU (BASELINE.json configs[3])'
+                                   % (a.voxel, a.latent, a.batch), 'global_batch': a.batch * world,
+                       'parallelism': 'dp%d, bucketed RCCL all-reduce of gradients, per-rank BatchNorm' % world},
+            'rccl_world_size': nranks, 'process_group': dist.get_backend() if dist is not None else None,
+            'global_metrics': global_metrics(sums), 'gradient_all_reduce': overlap,
+            'roofline': roof, 'cpu_baseline': cpu,
+            'final_loss_shape': float(metrics[0]), 'final_loss_kl': float(kl.mean())}
 
 
 # ------------------------------------------------------------------------------------------------ dry run (CPU rehearsal)
@@ -480,18 +530,18 @@ def main():
     lm = {n: v for n, v, _ in workload.layer_macs(cfg)}
     dominant, breakdown = 'D4', None
     single = None
-    pre = {'one_stream_layer_breakdown': 0, 'one_stream_rate': 0, 'schedule_preparation': 0}   # steps that run BEFORE the W warm-up steps
-    if not a.no_breakdown:
-        for _ in range(3):                      # weight packing, allocator growth and clock ramp happen here
-            step1()
-        torch.cuda.synchronize()
+    pre = {'weight_packing': 3, 'one_stream_layer_breakdown': 0, 'one_stream_rate': 0, 'schedule_preparation': 0}   # steps that run BEFORE the W warm-up steps
+    for _ in range(3):                          # weight packing, allocator growth and clock ramp happen here
+        step1()
+    torch.cuda.synchronize()
+    if a.full and not a.no_breakdown:
         t = E.LayerTimer()
         model._enc_eng.timer = model._dec_eng.timer = t
         for _ in range(10):
             step1()
         torch.cuda.synchronize()
         model._enc_eng.timer = model._dec_eng.timer = None
-        pre['one_stream_layer_breakdown'] = 13
+        pre['one_stream_layer_breakdown'] = 10
         breakdown = {k: round(float(np.median([e0.elapsed_time(e1) for e0, e1 in v])), 4) for k, v in t.events.items()}
         dominant = max(breakdown, key=breakdown.get)
         if nstreams > 1:
@@ -505,7 +555,7 @@ def main():
             ev_ = ti.events[dominant][-100:]
             single = {'streams': 1, 'value': a.batch / dt1, 'ms_per_step': 1e3 * dt1, 'steps': 100,
                       'dominant_launch_ms': float(np.mean([e0.elapsed_time(e1) for e0, e1 in ev_])), 'dominant_launches_timed': len(ev_)}
-    tm = E.LayerTimer(only=dominant)
+    tm = E.LayerTimer(only=dominant) if a.full else None
     for m_ in ev.models:                            # the dominant kernel is timed on whichever stream it is launched on
         m_._enc_eng.timer = m_._dec_eng.timer = tm
 
@@ -524,30 +574,32 @@ def main():
     for _ in range(a.warmup):
         step()
     ev.synchronize()
-    tm.events.clear()
+    if tm is not None:
+        tm.events.clear()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     el = time.perf_counter() - t0
-    nl, kms = tm.summary_ms()[dominant]
+    nl, kms = tm.summary_ms()[dominant] if tm is not None else (0, None)
 
-    # ---- the 8 metric scalars of the last step, summed over the ranks by ONE all-reduce (+ MAX of the timed region)
+    # ---- the 8 metric scalars of the last timed step, summed over the ranks by ONE all-reduce (+ MAX of the timed region)
     for m_ in ev.models:
         m_._enc_eng.timer = m_._dec_eng.timer = None
-    pred, stats, metrics, kl = step1()
-    torch.cuda.synchronize()
+    pred, stats, metrics, kl = last
     sums, el, nranks = reduce_metrics(dist, metric_vector(stats, kl), el, dev)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, [('pred', pred), ('stats', stats), ('metrics', metrics), ('kl', kl)])
 
-    # ---- parity gate + CPU baseline + secondary legs (rank 0, N == 1 only): AFTER the timed region -- the oracle's OpenMP
+    # ---- parity gate + CPU baseline + secondary legs (--full; rank 0, N == 1 only): AFTER the timed region -- the oracle's OpenMP
     # team spin-waits on every host core and would starve the launch thread
     cpu, cpu_torch, parity, f32_leg, h2d, cfg1, trained = None, None, None, None, None, None, None
-    if rank == 0 and world == 1 and a.cpu_samples > 0:
+    if a.full and rank == 0 and world == 1 and a.cpu_samples > 0:
         if a.voxel in (32, 64):
             trained = trained_parity(a, dev, build_model)
         ref, cpu = cpu_baseline(cfg, ep, dp, xh, epsh, a.cpu_samples)
@@ -657,20 +709,21 @@ def main():
 
     # ---- HBM traffic of the dominant kernel: only from a PMC summary taken on THESE kernel sources
     traffic, traffic_stale, traffic_src = None, None, None
-    try:
-        from profiles import summarize as _sm
-        cur = _sm.stamp(ROOT)['csrc_sha256']
-        cand = sorted(f for f in os.listdir(os.path.join(ROOT, 'profiles')) if f.endswith('_pmc_traffic.json'))
-        if cand and a.dtype == 'bf16' and a.batch == 256 and a.voxel == 32:
-            tj = json.load(open(os.path.join(ROOT, 'profiles', cand[-1])))
-            traffic_src = cand[-1]
-            if tj.get('stamp', {}).get('csrc_sha256') == cur:
-                traffic = tj['layers'].get(dominant, {}).get('hbm_bytes_per_launch')
-                traffic_stale = False
-            else:
-                traffic_stale = True
-    except Exception as e:       # a missing summary must not take the bench line down
-        traffic_src = 'unavailable: %s' % e
+    if a.full:
+        try:
+            from profiles import summarize as _sm
+            cur = _sm.stamp(ROOT)['csrc_sha256']
+            cand = sorted(f for f in os.listdir(os.path.join(ROOT, 'profiles')) if f.endswith('_pmc_traffic.json'))
+            if cand and a.dtype == 'bf16' and a.batch == 256 and a.voxel == 32:
+                tj = json.load(open(os.path.join(ROOT, 'profiles', cand[-1])))
+                traffic_src = cand[-1]
+                if tj.get('stamp', {}).get('csrc_sha256') == cur:
+                    traffic = tj['layers'].get(dominant, {}).get('hbm_bytes_per_launch')
+                    traffic_stale = False
+                else:
+                    traffic_stale = True
+        except Exception as e:       # a missing summary must not take the bench line down
+            traffic_src = 'unavailable: %s' % e
 
     def layer_dtype(name):
         if a.dtype != 'fp8':
@@ -703,16 +756,18 @@ def main():
         # other stream's kernels, so the duration between its events there includes the share of the chip it did not have: that
         # number is reported too (`in_timed_region`), the headline fraction is taken from the one-batch-at-a-time launches of the
         # same process (`single_stream`).  rocprofv3 summaries of both commands are under profiles/.
-        if single is not None:
-            roof = roofline_of(single['dominant_launch_ms'])
-            roof.update({'launch_ms': single['dominant_launch_ms'], 'launches_timed': single['dominant_launches_timed'],
-                         'measured': 'HIP events on the launch stream, one batch at a time (--streams 1 leg of this run)',
-                         'in_timed_region': dict(roofline_of(kms), launch_ms=kms, launches_timed=nl,
-                                                 note='%d streams: the kernel shares the chip with the other stream while its events are open' % nstreams)})
-        else:
-            roof = roofline_of(kms)
-            roof.update({'launch_ms': kms, 'launches_timed': nl, 'measured': 'HIP events on the launch stream inside the timed region'})
-        roof.update({'traffic': traffic, 'traffic_stale': traffic_stale, 'traffic_source': traffic_src})
+        roof = None
+        if a.full:
+            if single is not None:
+                roof = roofline_of(single['dominant_launch_ms'])
+                roof.update({'launch_ms': single['dominant_launch_ms'], 'launches_timed': single['dominant_launches_timed'],
+                             'measured': 'HIP events on the launch stream, one batch at a time (--streams 1 leg of this run)',
+                             'in_timed_region': dict(roofline_of(kms), launch_ms=kms, launches_timed=nl,
+                                                     note='%d streams: the kernel shares the chip with the other stream while its events are open' % nstreams)})
+            else:
+                roof = roofline_of(kms)
+                roof.update({'launch_ms': kms, 'launches_timed': nl, 'measured': 'HIP events on the launch stream inside the timed region'})
+            roof.update({'traffic': traffic, 'traffic_stale': traffic_stale, 'traffic_source': traffic_src})
         # the two HBM-bound ends of the path (north_star: "achieved HBM GB/s on the voxel load"): algorithmic bytes of one launch
         # over its HIP-event duration (one batch at a time, ~5 us of event overhead included) against the 8 TB/s spec, with the
         # counter bytes of the stamped PMC summary next to them
@@ -744,11 +799,11 @@ def main():
             'unit': 'reconstructions/s',
             'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
             'pre_timed_steps': dict(pre, total=sum(pre.values()), streams=nstreams,
-                                    note='steps run before the W warm-up steps: per-layer breakdown and one-batch-at-a-time rate on the caller\'s stream, '
+                                    note='steps run before the W warm-up steps: weight packing and (--full) per-layer breakdown and one-batch-at-a-time rate on the caller\'s stream, '
                                          'then 10 per stream so that every stream has its hardware queue and allocator pool; the timed region is exactly K steps'),
             'ms_per_step': 1e3 * el / a.steps,
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': a.dtype, 'data': 'synthetic', 'fp8_policy': a.fp8_policy if a.dtype == 'fp8' else None,
+            'dtype': a.dtype, 'data': 'synthetic', 'full': a.full, 'fp8_policy': a.fp8_policy if a.dtype == 'fp8' else None,
             'fp8_weight_rounding': ('e4m3fn, per-output-channel scale, error diffusion over the taps an output sums (voxvae/engine.py:quant_fp8)'
                                     if a.dtype == 'fp8' else None),
             'config': {'workload': 'ModelNet40 VAE getEval(missing_prob=0), %d^3 voxels, latent %d, batch %d per GPU, '

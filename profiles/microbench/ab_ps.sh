@@ -1,5 +1,5 @@
 #!/bin/bash
-run() { python bench.py --cpu-samples 0 $NB 2>/dev/null | python -c "
+run() { python bench.py --full --cpu-samples 0 $NB 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$TAG', '$NB', round(d['ms_per_step'], 4), (d.get('single_stream') or {}).get('ms_per_step'))

@@ -55,8 +55,8 @@ def test_bench_under_the_launcher_with_one_rank_takes_the_rccl_path():
     r = _last_json(p.stdout)
     assert r['n_gpus'] == 1 and r['rccl_world_size'] == 1 and r['process_group'] == 'nccl'
     assert r['value'] > 0 and r['global_metrics']['samples'] == 256
-    # training mode: gradient buckets through RCCL, with the overlap report the 8-GPU run will fill in
-    cmd = cmd[:cmd.index('--steps')] + ['--steps', '3', '--warmup', '2', '--mode', 'train']
+    # training mode: gradient buckets through RCCL, with the overlap report the 8-GPU run will fill in (a --full leg)
+    cmd = cmd[:cmd.index('--steps')] + ['--steps', '3', '--warmup', '2', '--mode', 'train', '--full']
     cmd[cmd.index('--master-port') + 1] = _env()['MASTER_PORT']
     p = subprocess.run(cmd, env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]

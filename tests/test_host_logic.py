@@ -343,6 +343,30 @@ def test_bench_dry_run_at_the_target_world_size_of_8():
     assert gb['wire'] == 'bf16' and gb['summed_correctly'] is True and gb['buckets'] >= 2
 
 
+def test_bench_dump_outputs_stays_within_budget_and_is_reproducible(tmp_path):
+    """bench.py --dump-outputs: float32 (float64 and integer counts as float64), whole arrays while they fit, a fixed seeded sample of
+    the largest one when they do not (64^3 at batch 64 = 67 MB of probabilities), the same files from run to run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    small = [('stats', torch.from_numpy(rng.random((16, 4)).astype(np.float32))), ('metrics', torch.arange(4, dtype=torch.int32)),
+             ('kl', torch.from_numpy(rng.random(16)))]
+    bench.dump_outputs(str(tmp_path / 'a'), [('pred', torch.from_numpy(rng.random((16, 32, 32, 32, 1), np.float32)))] + small + [('none', None)])
+    got = {f[:-4]: np.load(tmp_path / 'a' / f) for f in os.listdir(tmp_path / 'a')}
+    assert set(got) == {'pred', 'stats', 'metrics', 'kl'}
+    assert got['pred'].shape == (16, 32, 32, 32, 1) and got['pred'].dtype == np.float32
+    assert got['metrics'].dtype == np.float64 and list(got['metrics']) == [0, 1, 2, 3] and got['kl'].dtype == np.float64
+    big = torch.from_numpy(rng.random((64, 64, 64, 64, 1), np.float32))
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), [('pred', big)] + small)
+    files = sorted(os.listdir(tmp_path / 'b'))
+    assert sum(os.path.getsize(tmp_path / 'b' / f) for f in files) <= 64 * 10 ** 6
+    p = np.load(tmp_path / 'b' / 'pred.npy')
+    assert p.ndim == 1 and 0.9 * bench.DUMP_BYTES / 4 < p.size < big.numel()
+    assert np.isin(p[:100], big.numpy().ravel()).all()
+    assert all(np.array_equal(np.load(tmp_path / 'b' / f), np.load(tmp_path / 'c' / f)) for f in files)
+
+
 def test_bench_refuses_more_gpus_than_visible():
     """--gpus N with fewer than N visible GPUs fails loudly instead of running one rank (no GPU exists in this container)."""
     if torch.cuda.device_count() >= 2:
