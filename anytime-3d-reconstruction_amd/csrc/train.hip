@@ -1123,6 +1123,7 @@ VV_EXPORT int vv_wgrad_conv_k4s2(const void *src, const void *g, float *dw, int 
 
 VV_EXPORT int vv_unpack_meanpool_grad(const float *dpanel, float *dw, int side, int cin, int cout, void *stream) {
     if (!dpanel || !dw) return VV_ERR_NULL;
+    if (side <= 0 || cin <= 0 || cout <= 0) return VV_ERR_SHAPE;
     if (cin % 64 == 0 && cout % 64 == 0 && side > 0 && vv_aligned16(dpanel) && vv_aligned16(dw)) {
         VV_LAUNCH(unpack_meanpool_grad_tiled_kernel, dim3(64 * (cin / 64), cout / 64), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dpanel, dw,
                   side, cin, cout);
@@ -1135,6 +1136,7 @@ VV_EXPORT int vv_unpack_meanpool_grad(const float *dpanel, float *dw, int side, 
 
 VV_EXPORT int vv_unpack_convT_dense_grad(const float *dpanel, float *dw, int side, int cin, int cout, void *stream) {
     if (!dpanel || !dw) return VV_ERR_NULL;
+    if (side <= 0 || cin <= 0 || cout <= 0) return VV_ERR_SHAPE;
     VV_LAUNCH(unpack_convT_dense_grad_kernel, dim3(grid_1d((long)64 * cin * cout)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
               dpanel, dw, side, cin, cout);
     return vv_launch_status();
