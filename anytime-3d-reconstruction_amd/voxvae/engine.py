@@ -5,13 +5,15 @@ tensors), the packed MFMA panels derived from them and the layer chain, and driv
 (voxvae.lib).  torch is used for device memory and the current HIP stream only; every
 arithmetic step is a libvoxvae kernel.  Reference: src/net_core/autoencoder3D.py:72-139.
 """
+import collections
 import ctypes
-import os
+import functools
 
 import numpy as np
 import torch
 
 from . import lib as L
+from . import routes as R
 
 BN_EPS = 1e-3  # Keras BatchNormalization default (autoencoder3D.py:31)
 
@@ -112,7 +114,7 @@ def quant_fp8(w, cout_axis, tap_groups=None):
     shape = [1] * w.dim()
     shape[cout_axis] = -1
     ws = w / s.view(shape)
-    if tap_groups is None or os.environ.get('VV_FP8_SHAPED', '1') == '0':
+    if tap_groups is None or not R.switches().fp8_shaped:
         return round_e4m3(ws).contiguous(), s.contiguous()
     if w.dim() != 5 or w.shape[0] * w.shape[1] * w.shape[2] != 64:
         raise ValueError('tap groups are defined for [4,4,4,a,b] kernels, got %s' % (tuple(w.shape),))
@@ -127,9 +129,10 @@ def quant_fp8(w, cout_axis, tap_groups=None):
     return q.reshape(w.shape).contiguous(), s.contiguous()
 
 
-def fp8_layers_off():
-    """Layers kept on bf16 operands in 'fp8' mode: VV_FP8_OFF=E5,D2 (names as in bench.py's layer table)."""
-    return set(n for n in os.environ.get('VV_FP8_OFF', '').replace(' ', '').split(',') if n)
+# One stride-2 layer of an engine's plan (built by _pack, walked by forward, latent_tail and the trainer): the kernel form (a route of
+# voxvae/routes.py), the element types the kernel reads and writes, the weight image it reads (None in a training pack: the trainer's) and every
+# image the engine keeps for the layer, by kind.
+_Layer = collections.namedtuple('_Layer', 'name route idt odt w images')
 
 
 class _EngineBase:
@@ -149,29 +152,15 @@ class _EngineBase:
         self.tdt = _tdtype(self.dt)
         self.device = torch.device(device)
         self.params = {}          # name -> float32 CUDA tensor, Keras layout (the trainable/master copy)
-        self.packed = {}
+        self.packed = {}          # the other layers' images and every layer's folded vectors, by name
+        self.plan = []            # the stride-2 layers (_Layer), rebuilt by _pack
+        self.switches = R.switches()    # re-read by every _pack
         self.ws = _Workspace(self.device)
         self._dirty = True
         self._folded, self._want_fold = False, True
         self.act = L.ACT[structure['activation']]
         self.timer = None         # LayerTimer or None
         self.tag = ''
-
-    def _fp8_off(self):
-        """Layers kept on bf16 operands in 'fp8' mode: the VV_FP8_OFF override plus what the policy excludes.  'mid' and 'most' are policy
-        'all' minus a set: 'mid' keeps fp8 on the two widest stride-2 layers of each side (E2, E3 / D3, D4 of the five-layer models),
-        'most' only takes the encoder tail back (the layer whose error moves the whole latent)."""
-        off = set(fp8_layers_off())
-        pol, n = getattr(self, 'fp8_policy', 'wide'), len(self.filters)
-        enc = isinstance(self, EncoderEngine)
-        if pol in ('mid', 'most') and enc:
-            off.add('E%d' % n)
-        if pol == 'mid':
-            if enc:
-                off |= set('E%d' % (i + 1) for i in range(3, n - 1))
-            else:
-                off |= set('D%d' % (i + 1) for i in range(1, n - 3))
-        return off
 
     def _call(self, layer, fn, *args):
         t = self.timer
@@ -187,7 +176,7 @@ class _EngineBase:
             if k in self.params and tuple(self.params[k].shape) != tuple(t.shape):
                 raise ValueError('%s: shape %s != %s' % (k, tuple(t.shape), tuple(self.params[k].shape)))
             self.params[k] = t.to(self.device).contiguous()
-        self._dirty = True
+        self.weights_changed()
 
     def get_params(self):
         return {k: v.detach().cpu().numpy() for k, v in self.params.items()}
@@ -206,8 +195,39 @@ class _EngineBase:
     def _empty(self, *shape, dtype=None):
         return torch.empty(shape, dtype=dtype or self.tdt, device=self.device)
 
-    def _quant_fp8(self, w, cout_axis):
-        return quant_fp8(w, cout_axis, CONV_TAP_GROUPS if cout_axis == 4 else CONVT_TAP_GROUPS)
+    def _plan_layers(self, direction, sw):
+        """-> (route of every stride-2 layer, the layers the fp8 policy keeps on bf16); self.switches = sw from now on."""
+        self.switches = sw
+        f, n, enc = self.filters, len(self.filters), direction == R.CONV
+        off = R.fp8_layers_off(self.fp8_policy, enc, n, sw) if self.fp8 else ()
+        wide = self.fp8 and self.fp8_policy == 'wide'
+        routes = []
+        for i in range(1, n - 1):
+            want = self.fp8 and ('%s%d' % ('E' if enc else 'D', i + 1)) not in off
+            if enc:
+                routes.append(R.conv_route(self.D >> i, f[i - 1], f[i], self.dt, want, wide, False, sw))
+            else:
+                routes.append(R.convT_route(self.S << (i - 1), f[i - 1], f[i], self.dt, want, wide, sw))
+        return routes, off
+
+    def _pack_layer(self, direction, i, route, st):
+        """Weight images (routes.ENGINE_IMAGES) and folded BatchNorm vectors of stride-2 layer i -> {kind: image}."""
+        wname, bn, cout_axis, taps = ('conv%d/kernel', 'bn%d', 4, CONV_TAP_GROUPS) if direction == R.CONV else ('convT%d/kernel', 'bnT%d', 3, CONVT_TAP_GROUPS)
+        cin, cout, pk = self.filters[i - 1], self.filters[i], self.packed
+        q = route.endswith('_fp8')
+        wk = self.params[wname % i]
+        if q:
+            wk, qs = quant_fp8(wk, cout_axis, taps)
+        kinds = R.ENGINE_IMAGES[direction][route][0 if self._want_fold else 1]
+        images = {k: R.pack_image(direction, k, wk, cin, cout, L.VV_FP8 if q else self.dt, st) for k in kinds[:1]}
+        pk['scale%d' % i], pk['shift%d' % i] = self._fold(bn % i, cout)
+        for k in kinds[1:]:
+            images[k] = R.pack_image(direction, k, self.params[wname % i], cin, cout, self.dt, st)
+        if q:
+            pk['q%d' % i] = True
+            if pk['scale%d' % i] is not None:
+                pk['scale%d' % i].mul_(qs)
+        return images
 
     def _as_fp8(self, h, label):
         """bf16 activation -> fp8 copy (the hand-over from a bf16-only layer into an fp8 stretch)."""
@@ -215,10 +235,22 @@ class _EngineBase:
         self._call(label, 'vv_convert', L.ptr(h), L.ptr(o), h.numel(), L.VV_BF16, L.VV_FP8, _stream())
         return o
 
+    def needs_pack(self, fold=True):
+        """True when the next ensure_packed(fold) will repack: the weights changed, or the folded vectors are wanted and stale."""
+        return self._dirty or (fold and not self._folded)
+
+    def weights_changed(self):
+        self._dirty = True
+
+    def statistics_moved(self):
+        """A training-mode forward updated the moving statistics in place: the folded inference scale / shift vectors are stale (the
+        weight images are not)."""
+        self._folded = False
+
     def ensure_packed(self, fold=True):
         """Refresh the packed weight images after a weight change.  fold=False (the training step, which uses batch
         statistics) skips the folded moving-statistics scale/shift vectors; the next inference call packs them."""
-        if self._dirty or (fold and not self._folded):
+        if self.needs_pack(fold):
             self._want_fold = fold
             self._pack()
             self._dirty = False
@@ -273,58 +305,38 @@ class EncoderEngine(_EngineBase):
         return shp
 
     def _pack(self):
-        p, f, st = self.params, self.filters, _stream()
-        self.packed = {'scale0': None}
-        self.packed['scale0'], self.packed['shift0'] = self._fold('bn0', f[0])
-        self.packed['w0'] = self._empty(f[0], 64)
-        L.call('vv_pack_conv_k4', L.ptr(p['conv0/kernel']), L.ptr(self.packed['w0']), 1, f[0], self.dt, st)
-        for i in range(1, len(f) - 1):
-            # Cin 64 (the second layer) has an fp8 form too (tap-pair rows); VV_FP8_E2=0 keeps it on the bf16 direct kernel
-            q = self.fp8 and (f[i - 1] % 128 == 0 or (f[i - 1] == 64 and os.environ.get('VV_FP8_E2', '1') != '0')) \
-                and ('E%d' % (i + 1)) not in self._fp8_off()
-            if q and self.fp8_policy == 'wide':
-                q = bool(L.load().vv_conv3d_k4s2_direct_fp8_supported(self.D >> i, f[i - 1], f[i])) and os.environ.get('VV_FP8_E2', '1') != 'igemm'
-            wk = p['conv%d/kernel' % i]
-            if q:
-                wk, qs = self._quant_fp8(wk, 4)
-            small = (not q and not os.environ.get('VV_NO_SKIP')
-                     and bool(L.load().vv_conv3d_k4s2_skip_supported(self.D >> i, f[i - 1], f[i], self.dt)
-                              or L.load().vv_conv3d_k4s2_pos_supported(self.D >> i, f[i - 1], f[i], self.dt)))
-            if small and not self._want_fold:
-                w = None        # the training step packs the skip / position image of this layer per use (voxvae/train.py: _conv)
-            else:
-                w = self._empty(f[i], 64 * f[i - 1], dtype=torch.uint8 if q else None)
-                L.call('vv_pack_conv_k4', L.ptr(wk), L.ptr(w), f[i - 1], f[i], L.VV_FP8 if q else self.dt, st)
-            self.packed['w%d' % i] = w
-            self.packed['scale%d' % i], self.packed['shift%d' % i] = self._fold('bn%d' % i, f[i])
-            if q:
-                self.packed['q%d' % i] = True
-                if self.packed['scale%d' % i] is not None:
-                    self.packed['scale%d' % i].mul_(qs)
-            elif (self._want_fold and not os.environ.get('VV_NO_SKIP')
-                  and (L.load().vv_conv3d_k4s2_skip_supported(self.D >> i, f[i - 1], f[i], self.dt)
-                       or L.load().vv_conv3d_k4s2_pos_supported(self.D >> i, f[i - 1], f[i], self.dt))):
-                # the 8^3 -> 4^3 layer: whole samples resident in LDS, padded taps skipped; the 4^3 -> 2^3 layer: position-major
-                # split-K GEMM -- same [tap][Cin/64][Cout][64] panel (inference path; the training step keeps the implicit-GEMM
-                # panel above, which also serves its data-gradient passes)
-                ws = self._empty(64 * f[i - 1] * f[i])
-                L.call('vv_pack_conv_k4_skip', L.ptr(p['conv%d/kernel' % i]), L.ptr(ws), f[i - 1], f[i], st)
-                self.packed['ws%d' % i] = ws
-        i = len(f) - 1
-        if self.pool_max or self.pool_none:
+        p, f, st, pk = self.params, self.filters, _stream(), {}
+        routes, off = self._plan_layers(R.CONV, R.switches())
+        n, self.packed, self.plan = len(f), pk, []
+        pk['scale0'], pk['shift0'] = self._fold('bn0', f[0])
+        pk['w0'] = R.pack_image(R.CONV, 'igemm', p['conv0/kernel'], 1, f[0], self.dt, st)
+        pooled = not (self.pool_max or self.pool_none)
+        tail_fp8 = pooled and self.fp8 and self.fp8_policy != 'wide' and (self.S ** 3 * f[n - 2]) % 128 == 0 and ('E%d' % n) not in off
+        fp8, self._tail_fp8 = [r.endswith('_fp8') for r in routes] + [tail_fp8], tail_fp8
+        # element type of the first layer's output: the engine's dtype, or fp8 when the second layer is fp8 and the first layer's
+        # plane-form kernel applies (it stores e4m3fn itself)
+        self._h0_dt = L.VV_FP8 if (fp8[0] and self.D >= 32 and f[0] == 64 and self.dt == L.VV_BF16) else self.dt
+        for i, route in enumerate(routes, 1):
+            q, nq = fp8[i - 1], fp8[i]
+            images = self._pack_layer(R.CONV, i, route, st)
+            if nq and route in ('pos', 'skip'):     # these forms store the engine's dtype only; an fp8 next layer wants e4m3fn
+                route = R.conv_route(self.D >> i, f[i - 1], f[i], self.dt, False, False, False, self.switches._replace(no_skip=True))
+            self.plan.append(_Layer('E%d' % (i + 1), route, L.VV_FP8 if q else self.dt, L.VV_FP8 if nq else self.dt,
+                                    images.get(R.ROUTE_IMAGE[R.CONV][route]), images))
+        i = n - 1
+        if not pooled:
             # tf.reduce_max over the positions (autoencoder3D.py:92-93) / no pooling: the conv output itself is needed -> full panel [S^3 E][S^3 Cin]
             w = self._empty(self.S ** 3 * f[i], self.S ** 3 * f[i - 1])
             L.call('vv_pack_conv_k4s1_full', L.ptr(p['conv%d/kernel' % i]), L.ptr(w), self.S, f[i - 1], f[i], self.dt, st)
-            self.packed['w%d' % i] = w
+            pk['w%d' % i] = w
             return
-        q = self.fp8 and self.fp8_policy != 'wide' and (self.S ** 3 * f[i - 1]) % 128 == 0 and ('E%d' % (i + 1)) not in self._fp8_off()
         wk = p['conv%d/kernel' % i]
-        if q:
-            wk, qs = self._quant_fp8(wk, 4)
-            self.packed['q%d' % i], self.packed['scale%d' % i] = True, qs
-        w = self._empty(f[i], self.S ** 3 * f[i - 1], dtype=torch.uint8 if q else None)
-        L.call('vv_pack_conv_k4s1_meanpool', L.ptr(wk), L.ptr(w), self.S, f[i - 1], f[i], L.VV_FP8 if q else self.dt, st)
-        self.packed['w%d' % i] = w
+        if tail_fp8:
+            wk, qs = quant_fp8(wk, 4, CONV_TAP_GROUPS)
+            pk['q%d' % i], pk['scale%d' % i] = True, qs
+        w = self._empty(f[i], self.S ** 3 * f[i - 1], dtype=torch.uint8 if tail_fp8 else None)
+        L.call('vv_pack_conv_k4s1_meanpool', L.ptr(wk), L.ptr(w), self.S, f[i - 1], f[i], L.VV_FP8 if tail_fp8 else self.dt, st)
+        pk['w%d' % i] = w
 
     def forward(self, x, stop_before_tail=False, stop_before_pos=False):
         """x: float32 CUDA tensor [B,D,D,D,1] (contiguous) -> enc_out float32 [B,E].
@@ -337,59 +349,24 @@ class EncoderEngine(_EngineBase):
         if tuple(x.shape[1:]) != (D, D, D, 1) or x.dtype != torch.float32 or not x.is_contiguous():
             raise ValueError('encoder input must be contiguous float32 [B,%d,%d,%d,1], got %s %s' % (D, D, D, tuple(x.shape), x.dtype))
         side = D // 2
-        # element type of h: the engine's dtype, or fp8 inside an fp8 stretch (the first layer stores e4m3fn itself when the
-        # second layer is fp8 and its plane-form kernel applies)
-        hdt = L.VV_FP8 if (pk.get('q1', False) and D >= 32 and f[0] == 64 and self.dt == L.VV_BF16) else self.dt
+        hdt = self._h0_dt             # element type of h: the engine's dtype, or fp8 inside an fp8 stretch
         h = self._empty(B, side, side, side, f[0], dtype=torch.uint8 if hdt == L.VV_FP8 else None)
         self._call('E1', 'vv_conv3d_first_fwd_io', L.ptr(x), L.ptr(pk['w0']), L.ptr(pk['scale0']), L.ptr(pk['shift0']),
                L.ptr(h), B, D, f[0], self.act, self.dt, hdt, st)
-        for i in range(1, len(f) - 1):
-            q, nq = pk.get('q%d' % i, False), pk.get('q%d' % (i + 1), False)
-            odt = L.VV_FP8 if nq else self.dt
-            name = 'E%d' % (i + 1)
+        for i, ly in enumerate(self.plan, 1):
             if LAYER_INPUT_HOOK is not None:
-                h = LAYER_INPUT_HOOK(name, h)
-            if q:
-                if hdt != L.VV_FP8:
-                    h = self._as_fp8(h, name + 'c')
-                o = self._empty(B, side // 2, side // 2, side // 2, f[i], dtype=torch.uint8 if nq else None)
-                if (not os.environ.get('VV_NO_DIRECT') and os.environ.get('VV_FP8_E2', '1') != 'igemm' and odt != L.VV_F32
-                        and L.load().vv_conv3d_k4s2_direct_fp8_supported(side, f[i - 1], f[i])):
-                    # the widest encoder layer: fp8 twin of its direct kernel, same packed weights as the implicit GEMM
-                    self._call(name, 'vv_conv3d_k4s2_direct_fp8_fwd', L.ptr(h), L.ptr(pk['w%d' % i]), L.ptr(pk['scale%d' % i]),
-                               L.ptr(pk['shift%d' % i]), L.ptr(o), B, side, f[i - 1], f[i], self.act, odt, st)
-                else:
-                    ws = self.ws.get(L.load().vv_conv3d_k4s2_workspace_bytes(B, side, f[i - 1], f[i], L.VV_FP8))
-                    self._call(name, 'vv_conv3d_k4s2_fwd_io', L.ptr(h), L.ptr(pk['w%d' % i]), L.ptr(pk['scale%d' % i]), L.ptr(pk['shift%d' % i]),
-                               L.ptr(o), B, side, f[i - 1], f[i], self.act, L.VV_FP8, odt, L.ptr(ws), ws.numel(), st)
-                hdt = odt
-            elif ('ws%d' % i) in pk and not nq:
-                if stop_before_pos and stop_before_tail and side == 4 and i == len(f) - 2 and hdt == self.dt and not pk.get('q%d' % (i + 1), False):
-                    return h
-                o = self._empty(B, side // 2, side // 2, side // 2, f[i])
-                if side == 4:
-                    ws = self.ws.get(L.load().vv_conv3d_k4s2_pos_workspace_bytes(B, f[i - 1], f[i]))
-                    self._call(name, 'vv_conv3d_k4s2_pos_fwd', L.ptr(h), L.ptr(pk['ws%d' % i]), L.ptr(pk['scale%d' % i]),
-                               L.ptr(pk['shift%d' % i]), L.ptr(o), B, side, f[i - 1], f[i], self.act, self.dt, L.ptr(ws), ws.numel(), st)
-                else:
-                    self._call(name, 'vv_conv3d_k4s2_skip_fwd', L.ptr(h), L.ptr(pk['ws%d' % i]), L.ptr(pk['scale%d' % i]),
-                               L.ptr(pk['shift%d' % i]), L.ptr(o), B, side, f[i - 1], f[i], self.act, self.dt, st)
-                hdt = odt
-            elif not os.environ.get('VV_NO_DIRECT') and L.load().vv_conv3d_k4s2_direct_supported(side, f[i - 1], f[i], self.dt):
-                o = self._empty(B, side // 2, side // 2, side // 2, f[i], dtype=torch.uint8 if nq else None)
-                self._call(name, 'vv_conv3d_k4s2_direct_fwd_io', L.ptr(h), L.ptr(pk['w%d' % i]), L.ptr(pk['scale%d' % i]),
-                           L.ptr(pk['shift%d' % i]), L.ptr(o), B, side, f[i - 1], f[i], self.act, self.dt, odt, st)
-                hdt = odt
-            else:
-                o = self._empty(B, side // 2, side // 2, side // 2, f[i], dtype=torch.uint8 if nq else None)
-                ws = self.ws.get(L.load().vv_conv3d_k4s2_workspace_bytes(B, side, f[i - 1], f[i], self.dt))
-                self._call(name, 'vv_conv3d_k4s2_fwd_io', L.ptr(h), L.ptr(pk['w%d' % i]), L.ptr(pk['scale%d' % i]), L.ptr(pk['shift%d' % i]),
-                           L.ptr(o), B, side, f[i - 1], f[i], self.act, self.dt, odt, L.ptr(ws), ws.numel(), st)
-                hdt = odt
-            h, side = o, side // 2
+                h = LAYER_INPUT_HOOK(ly.name, h)
+            if ly.idt == L.VV_FP8 and hdt != L.VV_FP8:
+                h = self._as_fp8(h, ly.name + 'c')
+            if stop_before_pos and stop_before_tail and ly.route == 'pos' and i == len(f) - 2:
+                return h
+            o = self._empty(B, side // 2, side // 2, side // 2, f[i], dtype=torch.uint8 if ly.odt == L.VV_FP8 else None)
+            R.launch_conv(functools.partial(self._call, ly.name), ly.route, self.ws, h, ly.w, pk['scale%d' % i], pk['shift%d' % i], o,
+                          B, side, f[i - 1], f[i], self.act, self.dt, ly.odt, st)
+            h, side, hdt = o, side // 2, ly.odt
         i = len(f) - 1
         K = side ** 3 * f[i - 1]
-        q = pk.get('q%d' % i, False)
+        q = self._tail_fp8
         if self.pool_max or self.pool_none:
             if stop_before_tail:
                 raise L.VoxVaeError("stop_before_tail: the fused latent tail folds the MEAN pool into its weights")
@@ -472,54 +449,17 @@ class DecoderEngine(_EngineBase):
         pk['w0'] = self._empty(S3 * f[0], lin)
         L.call('vv_pack_convT_k4s1_dense', L.ptr(p['convT0/kernel']), L.ptr(pk['w0']), self.S, self.ch, f[0], self.dt, st)
         pk['scale0'], pk['shift0'] = self._fold('bnT0', f[0], S3)
-        # fp8 mode: the stride-2 layers with Cin % 128 == 0 run on fp8 operands -- the 128 -> 64 layer on the fp8 twin of its
-        # direct kernel (VV_FP8_LAST=igemm: fp8 implicit GEMM, VV_FP8_LAST=0: bf16 direct kernel), the others on the implicit GEMM
-        for i in range(1, len(f) - 1):
-            side_i = self.S << (i - 1)
-            direct = not os.environ.get('VV_NO_DIRECT') and bool(L.load().vv_convT3d_k4s2_direct_supported(side_i, f[i - 1], f[i], self.dt))
-            q = self.fp8 and f[i - 1] % 128 == 0 and ('D%d' % (i + 1)) not in self._fp8_off()
-            mode = os.environ.get('VV_FP8_LAST', 'direct')
-            direct8 = q and direct and mode not in ('0', 'igemm') and bool(L.load().vv_convT3d_k4s2_direct_fp8_supported(side_i, f[i - 1], f[i]))
-            if q and self.fp8_policy == 'wide' and not direct8:
-                q = False
-            if q and direct and mode == '0':
-                q = False
-            wk = p['convT%d/kernel' % i]
-            if q:
-                wk, qs = self._quant_fp8(wk, 3)
-            if direct8:
-                pk['wq8f%d' % i] = self._empty(64 * f[i - 1] * f[i], dtype=torch.uint8)
-                L.call('vv_pack_convT_k4s2_frag_fp8', L.ptr(wk), L.ptr(pk['wq8f%d' % i]), f[i - 1], f[i], st)
-            elif (not q and not self._want_fold and not os.environ.get('VV_NO_SKIP')
-                  and (L.load().vv_convT3d_k4s2_skip_supported(side_i, f[i - 1], f[i], self.dt)
-                       or L.load().vv_convT3d_k4s2_pos_supported(side_i, f[i - 1], f[i], self.dt))):
-                pk['w%d' % i] = None    # training step: the skip / position image is packed per use (voxvae/train.py: _convT)
-            elif (not q and not self._want_fold and direct and not os.environ.get('VV_NO_WHOLE') and not os.environ.get('VV_NO_DIRECT')
-                  and L.load().vv_convT3d_k4s2_whole_supported(side_i, f[i - 1], f[i], self.dt)):
-                pk['w%d' % i] = None    # training step: this layer runs on the whole-sample kernel (image 'ww' below)
-            else:
-                pk['w%d' % i] = self._empty(8, f[i], 8 * f[i - 1], dtype=torch.uint8 if q else None)
-                L.call('vv_pack_convT_k4s2', L.ptr(wk), L.ptr(pk['w%d' % i]), f[i - 1], f[i], L.VV_FP8 if q else self.dt, st)
-            pk['scale%d' % i], pk['shift%d' % i] = self._fold('bnT%d' % i, f[i])
-            if q:
-                pk['q%d' % i] = True
-                if pk['scale%d' % i] is not None:
-                    pk['scale%d' % i].mul_(qs)
-            elif direct:
-                whole = not os.environ.get('VV_NO_WHOLE') and bool(L.load().vv_convT3d_k4s2_whole_supported(side_i, f[i - 1], f[i], self.dt))
-                if not (whole and not self._want_fold):       # (the training step runs the whole-sample kernel: no fragment image)
-                    pk['wf%d' % i] = self._empty(64 * f[i - 1] * f[i])
-                    L.call('vv_pack_convT_k4s2_frag', L.ptr(p['convT%d/kernel' % i]), L.ptr(pk['wf%d' % i]), f[i - 1], f[i], st)
-                if whole:
-                    # the 8^3 x 128 -> 16^3 x 64 layer of the 32^3 model: one whole sample resident in LDS per workgroup
-                    pk['ww%d' % i] = self._empty(64 * f[i - 1] * f[i])
-                    L.call('vv_pack_convT_k4s2_skip', L.ptr(p['convT%d/kernel' % i]), L.ptr(pk['ww%d' % i]), f[i - 1], f[i], st)
-            elif (self._want_fold and not os.environ.get('VV_NO_SKIP')
-                  and (L.load().vv_convT3d_k4s2_skip_supported(side_i, f[i - 1], f[i], self.dt)
-                       or L.load().vv_convT3d_k4s2_pos_supported(side_i, f[i - 1], f[i], self.dt))):
-                # the 4^3 -> 8^3 and 2^3 -> 4^3 layers (see the encoder's twins)
-                pk['ws%d' % i] = self._empty(64 * f[i - 1] * f[i])
-                L.call('vv_pack_convT_k4s2_skip', L.ptr(p['convT%d/kernel' % i]), L.ptr(pk['ws%d' % i]), f[i - 1], f[i], st)
+        routes, _ = self._plan_layers(R.CONVT, R.switches())
+        fp8 = [r.endswith('_fp8') for r in routes] + [False]
+        self._h1_dt = L.VV_FP8 if fp8[0] else self.dt            # D1 hands fp8 to an fp8 D2
+        self.plan = []
+        for i, route in enumerate(routes, 1):
+            images = self._pack_layer(R.CONVT, i, route, st)
+            # the implicit GEMM stores what the next layer reads; every other form stores the engine's dtype (an fp8 next layer converts
+            # it itself: cheaper than the implicit GEMM), the fp8 direct kernel optionally e4m3fn (forward: routes.final_takes_fp8)
+            odt = L.VV_FP8 if fp8[i] and route in ('igemm', 'igemm_fp8') else self.dt
+            self.plan.append(_Layer('D%d' % (i + 1), route, L.VV_FP8 if fp8[i - 1] else self.dt, odt,
+                                    images.get(R.ROUTE_IMAGE[R.CONVT][route]), images))
 
     def forward(self, z_act, target=None, want_logits=False, gamma=0.6, epsilon=1e-7, want_metrics=False, h1=None):
         """z_act: [B,L] in the activation dtype.  target: float32 [B,D,D,D,1] or None.
@@ -547,56 +487,22 @@ class DecoderEngine(_EngineBase):
             self._call('D0', 'vv_dense_fwd', L.ptr(z_act), L.ptr(pk['wd']), L.ptr(pk['scaled']), L.ptr(pk['shiftd']), L.ptr(t), B, lin,
                    self.L, self.act, self.dt, self.dt, L.ptr(ws), ws.numel(), st)
             ws = self.ws.get(L.load().vv_dense_workspace_bytes(B, n0, lin, self.dt))
-            hdt = L.VV_FP8 if pk.get('q1', False) else self.dt          # D1 hands fp8 to an fp8 D2
+            hdt = self._h1_dt
             h = self._empty(B, S, S, S, f[0], dtype=torch.uint8 if hdt == L.VV_FP8 else None)
             self._call('D1', 'vv_dense_fwd', L.ptr(t), L.ptr(pk['w0']), L.ptr(pk['scale0']), L.ptr(pk['shift0']), L.ptr(h), B, n0, lin,
                    self.act, self.dt, hdt, L.ptr(ws), ws.numel(), st)
         side = S
-        for i in range(1, len(f) - 1):
-            name = 'D%d' % (i + 1)
-            q, nq = pk.get('q%d' % i, False), pk.get('q%d' % (i + 1), False)
-            odt = L.VV_FP8 if nq else self.dt
+        for i, ly in enumerate(self.plan, 1):
             if LAYER_INPUT_HOOK is not None:
-                h = LAYER_INPUT_HOOK(name, h)
-            if ('ww%d' % i) in pk and hdt == self.dt:
-                o = self._empty(B, 2 * side, 2 * side, 2 * side, f[i])
-                self._call(name, 'vv_convT3d_k4s2_whole_fwd', L.ptr(h), L.ptr(pk['ww%d' % i]), L.ptr(pk['scale%d' % i]),
-                           L.ptr(pk['shift%d' % i]), L.ptr(o), B, side, f[i - 1], f[i], self.act, self.dt, st)
-                h, side, hdt = o, 2 * side, self.dt
-                continue
-            if ('wf%d' % i) in pk:
-                o = self._empty(B, 2 * side, 2 * side, 2 * side, f[i])
-                self._call(name, 'vv_convT3d_k4s2_direct_fwd', L.ptr(h), L.ptr(pk['wf%d' % i]), L.ptr(pk['scale%d' % i]),
-                           L.ptr(pk['shift%d' % i]), L.ptr(o), B, side, f[i - 1], f[i], self.act, self.dt, st)
-                h, side, hdt = o, 2 * side, self.dt
-                continue
-            if ('ws%d' % i) in pk and hdt == self.dt:      # (an fp8 next layer converts this bf16 output itself: cheaper than the implicit GEMM)
-                o = self._empty(B, 2 * side, 2 * side, 2 * side, f[i])
-                if side == 2:
-                    ws = self.ws.get(L.load().vv_convT3d_k4s2_pos_workspace_bytes(B, f[i - 1], f[i]))
-                    self._call(name, 'vv_convT3d_k4s2_pos_fwd', L.ptr(h), L.ptr(pk['ws%d' % i]), L.ptr(pk['scale%d' % i]),
-                               L.ptr(pk['shift%d' % i]), L.ptr(o), B, side, f[i - 1], f[i], self.act, self.dt, L.ptr(ws), ws.numel(), st)
-                else:
-                    self._call(name, 'vv_convT3d_k4s2_skip_fwd', L.ptr(h), L.ptr(pk['ws%d' % i]), L.ptr(pk['scale%d' % i]),
-                               L.ptr(pk['shift%d' % i]), L.ptr(o), B, side, f[i - 1], f[i], self.act, self.dt, st)
-                h, side, hdt = o, 2 * side, self.dt
-                continue
-            if q and hdt != L.VV_FP8:
-                h = self._as_fp8(h, name + 'c')
-            if ('wq8f%d' % i) in pk:                          # fp8 direct kernel: e4m3fn in, bf16 out
-                # VV_FP8_D5=1: hand e4m3fn to the fp8 form of the final layer (sweep form, large batches).  Off by default: it is
-                # 5 % faster at 32^3 and not at all at 64^3, and takes the IoU delta at 64^3 from 6e-5 to 4e-4 (gate 1e-3)
-                o8 = (i == len(f) - 2 and 2 * side >= 8 and B * ((2 * side) // 8) ** 2 >= 128 and os.environ.get('VV_FP8_D5', '0') == '1')
-                o = self._empty(B, 2 * side, 2 * side, 2 * side, f[i], dtype=torch.uint8 if o8 else None)
-                self._call(name, 'vv_convT3d_k4s2_direct_fp8_fwd', L.ptr(h), L.ptr(pk['wq8f%d' % i]), L.ptr(pk['scale%d' % i]),
-                           L.ptr(pk['shift%d' % i]), L.ptr(o), B, side, f[i - 1], f[i], self.act, L.VV_FP8 if o8 else self.dt, st)
-                h, side, hdt = o, 2 * side, (L.VV_FP8 if o8 else self.dt)
-                continue
-            idt = L.VV_FP8 if q else self.dt
-            ws = self.ws.get(L.load().vv_convT3d_k4s2_workspace_bytes(B, side, f[i - 1], f[i], idt))
-            o = self._empty(B, 2 * side, 2 * side, 2 * side, f[i], dtype=torch.uint8 if nq else None)
-            self._call(name, 'vv_convT3d_k4s2_fwd_io', L.ptr(h), L.ptr(pk['w%d' % i]), L.ptr(pk['scale%d' % i]), L.ptr(pk['shift%d' % i]),
-                   L.ptr(o), B, side, f[i - 1], f[i], self.act, idt, odt, L.ptr(ws), ws.numel(), st)
+                h = LAYER_INPUT_HOOK(ly.name, h)
+            if ly.idt == L.VV_FP8 and hdt != L.VV_FP8:
+                h = self._as_fp8(h, ly.name + 'c')
+            odt = ly.odt
+            if ly.route == 'direct_fp8' and i == len(f) - 2 and R.final_takes_fp8(2 * side, B, self.switches):
+                odt = L.VV_FP8
+            o = self._empty(B, 2 * side, 2 * side, 2 * side, f[i], dtype=torch.uint8 if odt == L.VV_FP8 else None)
+            R.launch_convT(functools.partial(self._call, ly.name), ly.route, self.ws, h, ly.w, pk['scale%d' % i], pk['shift%d' % i], o,
+                           B, side, f[i - 1], f[i], self.act, self.dt, odt, st)
             h, side, hdt = o, 2 * side, odt
         if target is None:
             target = torch.zeros(B, D, D, D, 1, dtype=torch.float32, device=self.device)
@@ -636,32 +542,23 @@ def latent_tail_supported(enc, dec, variational):
     """True when encoder tail -> reparam/KL -> Dense -> first decoder layer can run as the two fused launches of latent_tail.hip."""
     if getattr(enc, 'pool_max', False) or getattr(enc, 'pool_none', False) or getattr(enc, 'final_sigmoid', False):
         return False
-    if enc.dt != L.VV_BF16 or enc.fp8 or dec.fp8 or dec.dt != L.VV_BF16 or os.environ.get('VV_NO_LATENT_TAIL'):
+    if enc.dt != L.VV_BF16 or enc.fp8 or dec.fp8 or dec.dt != L.VV_BF16 or enc.act != dec.act:
         return False
-    Lz = dec.L
-    K5 = enc.S ** 3 * enc.filters[-2]
-    # Measured: at the 32^3 model (K5 = n1 = 4096) the two fused launches take 0.028 ms against 0.045 ms for the five calls;
-    # at the 64^3 model (K5 = n1 = 32768: 128 K slices of float32 slabs to sum, 8x the seed columns) 0.197 ms against 0.06 ms.
-    if K5 > 8192 or dec.S ** 3 * dec.filters[0] > 8192:
-        return False
-    return bool(L.load().vv_latent_tail_supported(K5, enc.E, Lz, dec.S ** 3 * dec.ch, dec.S ** 3 * dec.filters[0], int(variational), L.VV_BF16)) \
-        and enc.act == dec.act
+    return R.fused_tail(enc.S ** 3 * enc.filters[-2], enc.E, dec.L, dec.S ** 3 * dec.ch, dec.S ** 3 * dec.filters[0], int(variational), enc.switches)
 
 
 def pos_latent_tail_supported(enc, dec, variational, batch=1):
     """True when the last stride-2 encoder layer (4^3 -> 2^3, position-major form) and the latent tail can run as ONE fused call
     (vv_conv_pos_latent_tail_fwd: the layer's split-K partial sums are summed inside the tail; one launch, so the batch's layer
     input has to fit 32-bit buffer offsets)."""
-    if not latent_tail_supported(enc, dec, variational) or os.environ.get('VV_NO_POS_TAIL') or enc.S != 2 or len(enc.filters) < 3:
+    if not latent_tail_supported(enc, dec, variational) or enc.switches.no_pos_tail or enc.S != 2 or len(enc.filters) < 3:
         return False
     if batch * 64 * enc.filters[-3] * 2 > 0x7FFFFFFF:
         return False
-    ne = len(enc.filters) - 1
     enc.ensure_packed()
-    if ('ws%d' % (ne - 1)) not in enc.packed or enc.packed.get('q%d' % (ne - 1), False):
+    if enc.plan[-1].route != 'pos':
         return False
-    return bool(L.load().vv_conv_pos_latent_tail_supported(enc.filters[-3], enc.filters[-2], enc.E, dec.L, dec.S ** 3 * dec.ch,
-                                                           dec.S ** 3 * dec.filters[0], int(variational), L.VV_BF16))
+    return R.fused_pos_tail(enc.filters[-3], enc.filters[-2], enc.E, dec.L, dec.S ** 3 * dec.ch, dec.S ** 3 * dec.filters[0], int(variational))
 
 
 def latent_tail(enc, dec, h, eps, variational, want_enc_out=False, pos_layer=False):
@@ -676,33 +573,25 @@ def latent_tail(enc, dec, h, eps, variational, want_enc_out=False, pos_layer=Fal
     K5 = enc.S ** 3 * enc.filters[-2]
     lin, n1 = dec.S ** 3 * dec.ch, dec.S ** 3 * dec.filters[0]
     ne = len(enc.filters) - 1
-    if pos_layer:
-        if tuple(h.shape[1:]) != (4, 4, 4, enc.filters[-3]):
-            raise L.VoxVaeError('latent_tail(pos_layer=True) takes the [B,4,4,4,%d] input of the last stride-2 layer, got %s' % (enc.filters[-3], tuple(h.shape)))
-        z = torch.empty(B, Lz, dtype=torch.float32, device=dev)
-        z_act = torch.empty(B, Lz, dtype=torch.bfloat16, device=dev)
-        kl = torch.empty(B, dtype=torch.float32, device=dev) if variational else None
-        enc_out = torch.empty(B, E, dtype=torch.float32, device=dev) if want_enc_out else None
-        h1 = torch.empty(B, dec.S, dec.S, dec.S, dec.filters[0], dtype=torch.bfloat16, device=dev)
-        c3, c4 = enc.filters[-3], enc.filters[-2]
-        ws = enc.ws.get(L.load().vv_conv_pos_latent_tail_workspace_bytes(B, c3, c4, E))
-        pe, pd = enc.packed, dec.packed
-        i4 = ne - 1
-        enc._call('E%dLT' % ne, 'vv_conv_pos_latent_tail_fwd', L.ptr(h), L.ptr(pe['ws%d' % i4]), L.ptr(pe['scale%d' % i4]), L.ptr(pe['shift%d' % i4]),
-                  c3, c4, L.ptr(pe['w%d' % ne]), L.ptr(pe.get('scale%d' % ne)), L.ptr(eps), L.ptr(pd['wd']), L.ptr(pd['scaled']), L.ptr(pd['shiftd']),
-                  L.ptr(pd['w0']), L.ptr(pd['scale0']), L.ptr(pd['shift0']), L.ptr(enc_out), L.ptr(z), L.ptr(z_act), L.ptr(kl), L.ptr(h1), B, E, Lz,
-                  lin, n1, int(variational), dec.act, L.VV_BF16, L.ptr(ws), ws.numel(), _stream())
-        return z, z_act, kl, enc_out, h1
+    if pos_layer and tuple(h.shape[1:]) != (4, 4, 4, enc.filters[-3]):
+        raise L.VoxVaeError('latent_tail(pos_layer=True) takes the [B,4,4,4,%d] input of the last stride-2 layer, got %s' % (enc.filters[-3], tuple(h.shape)))
     z = torch.empty(B, Lz, dtype=torch.float32, device=dev)
     z_act = torch.empty(B, Lz, dtype=torch.bfloat16, device=dev)
     kl = torch.empty(B, dtype=torch.float32, device=dev) if variational else None
     enc_out = torch.empty(B, E, dtype=torch.float32, device=dev) if want_enc_out else None
     h1 = torch.empty(B, dec.S, dec.S, dec.S, dec.filters[0], dtype=torch.bfloat16, device=dev)
-    ws = enc.ws.get(L.load().vv_latent_tail_workspace_bytes(B, K5, E, n1))
     pe, pd = enc.packed, dec.packed
-    enc._call('LT', 'vv_latent_tail_fwd', L.ptr(h), L.ptr(pe['w%d' % ne]), L.ptr(pe.get('scale%d' % ne)), L.ptr(eps), L.ptr(pd['wd']),
-              L.ptr(pd['scaled']), L.ptr(pd['shiftd']), L.ptr(pd['w0']), L.ptr(pd['scale0']), L.ptr(pd['shift0']), L.ptr(enc_out), L.ptr(z),
-              L.ptr(z_act), L.ptr(kl), L.ptr(h1), B, K5, E, Lz, lin, n1, int(variational), dec.act, L.VV_BF16, L.ptr(ws), ws.numel(), _stream())
+    tail = (L.ptr(pe['w%d' % ne]), L.ptr(pe.get('scale%d' % ne)), L.ptr(eps), L.ptr(pd['wd']), L.ptr(pd['scaled']), L.ptr(pd['shiftd']),
+            L.ptr(pd['w0']), L.ptr(pd['scale0']), L.ptr(pd['shift0']), L.ptr(enc_out), L.ptr(z), L.ptr(z_act), L.ptr(kl), L.ptr(h1), B)
+    if pos_layer:
+        c3, c4, i4 = enc.filters[-3], enc.filters[-2], ne - 1
+        ws = enc.ws.get(L.load().vv_conv_pos_latent_tail_workspace_bytes(B, c3, c4, E))
+        enc._call('E%dLT' % ne, 'vv_conv_pos_latent_tail_fwd', L.ptr(h), L.ptr(enc.plan[-1].w), L.ptr(pe['scale%d' % i4]), L.ptr(pe['shift%d' % i4]),
+                  c3, c4, *tail, E, Lz, lin, n1, int(variational), dec.act, L.VV_BF16, L.ptr(ws), ws.numel(), _stream())
+    else:
+        ws = enc.ws.get(L.load().vv_latent_tail_workspace_bytes(B, K5, E, n1))
+        enc._call('LT', 'vv_latent_tail_fwd', L.ptr(h), *tail, K5, E, Lz, lin, n1, int(variational), dec.act, L.VV_BF16, L.ptr(ws), ws.numel(),
+                  _stream())
     return z, z_act, kl, enc_out, h1
 
 

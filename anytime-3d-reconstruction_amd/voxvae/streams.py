@@ -17,6 +17,11 @@ Measured on MI355X (32^3, batch 256, bf16; profiles/microbench/mb_streams3.py, f
 import torch
 
 
+def _engines(model):
+    """The engines of a model (the image -> 3D model has no voxel encoder)."""
+    return [e for e in (getattr(model, '_enc_eng', None), getattr(model, '_dec_eng', None)) if e is not None]
+
+
 class StreamedEvaluator:
     def __init__(self, model_factory, streams=3, device=None, replicas=False, priorities=None):
         """priorities: optional list of HIP stream priorities (0 = normal, -1 = high), one per stream (an experiment knob: a stream that
@@ -38,15 +43,15 @@ class StreamedEvaluator:
         are still being written (and the repack frees the old images while other streams may still read them).  So the pack runs
         here, on the caller's stream, after every stream has drained what it had in flight, and every stream's next step waits for
         it (an event: the caller may issue its next submit from another stream)."""
-        enc, dec = model._enc_eng, model._dec_eng
-        if not (enc._dirty or dec._dirty or not enc._folded or not dec._folded):
+        engines = _engines(model)
+        if not any(e.needs_pack() for e in engines):
             return
         cur = torch.cuda.current_stream(self.device)
         for s in self.streams:
             if s is not None:
                 cur.wait_stream(s)
-        enc.ensure_packed()
-        dec.ensure_packed()
+        for e in engines:
+            e.ensure_packed()
         self._pack_event = torch.cuda.Event()
         self._pack_event.record(cur)
         self._pack_pending = set(id(s) for s in self.streams if s is not None)
@@ -123,8 +128,8 @@ class HostPipeline:
     def submit(self, inputs, category_vectors, missing_prob=0.0, **kw):
         m = self.model
         cur = torch.cuda.current_stream(self.device)
-        engines = [e for e in (getattr(m, '_enc_eng', None), getattr(m, '_dec_eng', None)) if e is not None]   # (the image -> 3D model has no voxel encoder)
-        if any(e._dirty or not e._folded for e in engines):
+        engines = _engines(m)
+        if any(e.needs_pack() for e in engines):
             for s in self.streams:                  # weight images are shared by the streams: repack with nothing in flight
                 cur.wait_stream(s)
             for e in engines:

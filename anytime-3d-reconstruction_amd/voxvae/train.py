@@ -17,6 +17,7 @@ import torch
 
 from . import engine as E
 from . import lib as L
+from . import routes as R
 
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99          # Keras BatchNormalization defaults
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-7   # tf.keras.optimizers.Adam defaults
@@ -214,37 +215,31 @@ class Trainer:
             raise ValueError('encoder and decoder engines must share one activation dtype')
         if dec.fp8 or (enc is not None and enc.fp8):
             raise ValueError("fit() runs in 'f32' or 'bf16'; 'fp8' is an inference mode (quantised weight images)")
-        if enc is not None and (getattr(enc, 'pool_none', False) or getattr(enc, 'final_sigmoid', False)):
+        if enc is not None and (enc.pool_none or enc.final_sigmoid):
             raise NotImplementedError("fit() with final_pool='None' / an encoder final_activation: inference only (no reference config trains with them)")
-        if enc is not None and getattr(enc, 'pool_max', False):
+        if enc is not None and enc.pool_max:
             raise NotImplementedError("fit() with final_pool='max': the training step folds the mean pool into the last conv's panel; "
                                       "no reference config trains with the max pool")
         # 'f32': everything on the exact-f32 MFMA path (parity mode).  'bf16': mixed precision -- activations, their
         # gradients and the MFMA operands in bf16, float32 master weights / Adam moments / BatchNorm statistics / losses,
         # weight gradients accumulated in float32 (f32 MFMA over widened operands).
-        self.dt = dec.dt
-        self.tdt = torch.bfloat16 if self.dt == L.VV_BF16 else torch.float32
-        self.enc, self.dec, self.var, self.lr = enc, dec, variational, float(learning_rate)   # enc None: decoder-only (image -> 3D model)
-        self.dev = dec.device
+        self._init_forward(enc, dec, variational)     # enc None: decoder-only (image -> 3D model)
+        self.lr = float(learning_rate)
         self.world, self.group = int(world_size), group
         self.t = 0
-        self.debug = None          # set to a dict to capture intermediate tensors of the next step (tests)
         self.overlap = True        # launch each gradient bucket's all-reduce as soon as its last member is enqueued
         # Weight gradients on a SECOND stream (round 4, opt-in: VOXVAE_WGRAD_STREAM=1): wgrad(layer i) needs only dL/d(conv out of i) and
         # the layer's input, and nothing downstream needs it before Adam, so it can fork off the chain while that continues with the next
         # layer's BatchNorm backward sweeps (HBM streams without LDS beside MFMA / LDS work).  Measured on MI355X it is SLOWER: 2.74 against
         # 2.65 ms per step, the weight-gradient kernels take 0.28 instead of 0.13 ms each beside the sweeps and nothing is gained back
         # (profiles/r04_train_wgrad_stream_ab.json) -- the same sign as round 3's side-stream weight packing.  Bit-identical results.
-        self.wgrad_stream = None
         if str(self.dev).startswith('cuda') and os.environ.get('VOXVAE_WGRAD_STREAM', '0') == '1':
             self.wgrad_stream = torch.cuda.Stream(device=self.dev)
-        self.ws = E._Workspace(self.dev)
         names = [] if enc is None else [('enc/' + k, v.shape) for k, v in enc.params.items() if not k.endswith(('moving_mean', 'moving_variance'))]
         names += [('dec/' + k, v.shape) for k, v in dec.params.items() if not k.endswith(('moving_mean', 'moving_variance'))]
         # backward order: decoder tail first ... encoder head last
         self.order = list(reversed(names))
         self.grads = GradBuckets(self.order, self.dev, wire=grad_wire or os.environ.get('VOXVAE_GRAD_WIRE', 'f32'), world_size=self.world)
-        self._side_used = False
         self.m = {n: torch.zeros(s, dtype=torch.float32, device=self.dev) for n, s in names}
         self.v = {n: torch.zeros(s, dtype=torch.float32, device=self.dev) for n, s in names}
 
@@ -256,23 +251,39 @@ class Trainer:
         if eng.fp8:
             raise ValueError("training=True runs in 'f32' or 'bf16'; 'fp8' is an inference mode")
         t = cls.__new__(cls)
-        t.enc, t.dec, t.dt = enc, dec, eng.dt
-        t.tdt = torch.bfloat16 if t.dt == L.VV_BF16 else torch.float32
-        t.dev, t.ws, t.debug, t.var = eng.device, E._Workspace(eng.device), None, False
+        t._init_forward(enc, dec, False)
         return t
 
-    def _moved_statistics(self, *engines):
-        """The moving statistics were updated in place by a training-mode forward: the folded inference scale / shift
-        vectors of these engines are stale (the weight images are not)."""
+    def _init_forward(self, enc, dec, variational):
+        """What the training-mode forward needs; all of a forward_only() Trainer, the start of a full one."""
+        eng = dec if dec is not None else enc
+        self.enc, self.dec, self.var = enc, dec, variational
+        self.dt, self.tdt, self.dev = eng.dt, E._tdtype(eng.dt), eng.device
+        self.ws = E._Workspace(self.dev)
+        self.sw = R.switches()     # re-read at the start of every entry point (_begin)
+        self.debug = None          # set to a dict to capture intermediate tensors of the next step (tests)
+        self.timer = None          # a LayerTimer: HIP events around the weight-gradient launches (bench.py's roofline leg)
+        self.wgrad_stream, self._side_used = None, False
+        self._prepacked = {}       # (direction, weight pointer, cin, cout) -> the step's batched 'skip' images (_prepack)
+        self._adam_ptrs = None
+
+    def _begin(self, *engines, step=False):
+        """Start of every entry point: the switches are read once, the engines packed without folded vectors (batch statistics); an
+        optimisation step also opens the gradient buckets and batches its weight images."""
+        self.sw = R.switches()
         for e in engines:
-            if e is not None:
-                e._folded = False
+            e.ensure_packed(fold=False)
+        if step:
+            self.grads.begin_step()
+            if self.wgrad_stream is not None:
+                self.grads.producer_streams = (torch.cuda.current_stream(self.dev), self.wgrad_stream)
+            self._prepack()
 
     def encoder_training_mode(self, x):
         """encoder(x, training=True): batch-statistics BatchNorm, moving statistics move; -> enc_out float32 [B, E]."""
-        self.enc.ensure_packed(fold=False)
+        self._begin(self.enc)
         enc_out, _ = self._encoder_forward(x, x.shape[0])
-        self._moved_statistics(self.enc)
+        self.enc.statistics_moved()
         return enc_out
 
     # ------------------------------------------------------------------ helpers
@@ -305,24 +316,18 @@ class Trainer:
         L.call('vv_convert', L.ptr(t), L.ptr(o), t.numel(), L.VV_F32, self.dt, _st())
         return o
 
-    def _bn_fwd(self, c, rows, ch, eng, prefix, act):
+    def _bn_fwd(self, c, rows, ch, eng, prefix, act, partial=None, nblocks=0):
+        """Batch statistics of c [rows, ch] (moving statistics updated in place), then BatchNorm + activation.  partial: the per-block
+        column sums the producer of c left (vv_convT3d_k4s2_whole_stats_fwd) -- finalised here instead of a sweep over c."""
         bn = _BN(ch, self.dev)
         p = eng.params
-        ws = self.ws.get(L.load().vv_bn_workspace_bytes(rows, ch))
-        L.call('vv_bn_train_stats', L.ptr(c), rows, ch, L.ptr(p[prefix + '/gamma']), L.ptr(p[prefix + '/beta']), BN_EPS, BN_MOMENTUM,
-               L.ptr(bn.mean), L.ptr(bn.var), L.ptr(bn.rstd), L.ptr(bn.scale), L.ptr(bn.shift), L.ptr(p[prefix + '/moving_mean']),
-               L.ptr(p[prefix + '/moving_variance']), self._dt(c), L.ptr(ws), ws.numel(), _st())
-        h = torch.empty_like(c)
-        L.call('vv_bn_act_fwd', L.ptr(c), L.ptr(bn.scale), L.ptr(bn.shift), L.ptr(h), rows, ch, act, self._dt(c), _st())
-        return h, bn
-
-    def _bn_fwd_from_partials(self, c, partial, nblocks, rows, ch, eng, prefix, act):
-        """_bn_fwd for a layer whose producer left the per-block column sums (vv_convT3d_k4s2_whole_stats_fwd): finalise + apply."""
-        bn = _BN(ch, self.dev)
-        p = eng.params
-        L.call('vv_bn_finalize_stats', L.ptr(partial), nblocks, rows, ch, L.ptr(p[prefix + '/gamma']), L.ptr(p[prefix + '/beta']), BN_EPS, BN_MOMENTUM,
-               L.ptr(bn.mean), L.ptr(bn.var), L.ptr(bn.rstd), L.ptr(bn.scale), L.ptr(bn.shift), L.ptr(p[prefix + '/moving_mean']),
-               L.ptr(p[prefix + '/moving_variance']), _st())
+        stats = (L.ptr(p[prefix + '/gamma']), L.ptr(p[prefix + '/beta']), BN_EPS, BN_MOMENTUM, L.ptr(bn.mean), L.ptr(bn.var), L.ptr(bn.rstd),
+                 L.ptr(bn.scale), L.ptr(bn.shift), L.ptr(p[prefix + '/moving_mean']), L.ptr(p[prefix + '/moving_variance']))
+        if partial is not None:
+            L.call('vv_bn_finalize_stats', L.ptr(partial), nblocks, rows, ch, *stats, _st())
+        else:
+            ws = self.ws.get(L.load().vv_bn_workspace_bytes(rows, ch))
+            L.call('vv_bn_train_stats', L.ptr(c), rows, ch, *stats, self._dt(c), L.ptr(ws), ws.numel(), _st())
         h = torch.empty_like(c)
         L.call('vv_bn_act_fwd', L.ptr(c), L.ptr(bn.scale), L.ptr(bn.shift), L.ptr(h), rows, ch, act, self._dt(c), _st())
         return h, bn
@@ -358,7 +363,7 @@ class Trainer:
         """Weight gradient of a stride-2 layer into `out` (a view of a gradient bucket).  ready: the gradient's name -- reported to
         the buckets from the stream the kernel was enqueued on (a bucket's all-reduce is ordered behind that stream)."""
         o = side // 2
-        ws_stream = getattr(self, 'wgrad_stream', None)
+        ws_stream = self.wgrad_stream
         if ws_stream is None:
             self._wgrad_conv_launch(src, g, out, batch, side, cin, cout, o)
             if ready:
@@ -376,94 +381,57 @@ class Trainer:
 
     def _wgrad_conv_launch(self, src, g, out, batch, side, cin, cout, o):
         ws = self.ws.get(L.load().vv_wgrad_workspace_bytes(batch * o ** 3, 64 * cin, cout))
-        tm = getattr(self, 'timer', None)            # bench.py's roofline leg: HIP events around the launch, on its stream
+        tm = self.timer                              # bench.py's roofline leg: HIP events around the launch, on its stream
         tok = tm.begin('wgrad:%d:%d:%d' % (side, cin, cout)) if tm is not None else None
         L.call('vv_wgrad_conv_k4s2', L.ptr(src), L.ptr(g), L.ptr(out), batch, side, cin, cout, self._dt(src), self._dt(g), L.ptr(ws),
                ws.numel(), _st())
         if tm is not None:
             tm.end(tok)
 
-    def _conv(self, x, w_keras, B, side, cin, cout, packed=None):
-        """Conv3D k4 s2 of x [B,side^3,cin] with a Keras kernel array read as [4,4,4,cin,cout]: the forward layers (packed =
-        the engine's image of the same weights) and the data gradients of the transposed layers (packed here)."""
-        dt, st = self.dt, _st()
-        wp = packed
-        y = self._aempty(B, side // 2, side // 2, side // 2, cout)
-        lib = L.load()
-        if not os.environ.get('VV_NO_SKIP') and (lib.vv_conv3d_k4s2_skip_supported(side, cin, cout, dt) or lib.vv_conv3d_k4s2_pos_supported(side, cin, cout, dt)):
-            # 8^3 -> 4^3 / 4^3 -> 2^3 (bf16): the whole-samples-in-LDS and position-major kernels of the evaluation path, raw output
-            # (no scale / shift / activation: BatchNorm follows with batch statistics); their weight image is packed per use
-            wsk = getattr(self, '_prepacked', {}).get((0, w_keras.data_ptr(), cin, cout))
-            if wsk is None:
-                wsk = self._aempty(64 * cin * cout)
-                L.call('vv_pack_conv_k4_skip', L.ptr(w_keras), L.ptr(wsk), cin, cout, st)
-            if side == 4:
-                ws = self.ws.get(lib.vv_conv3d_k4s2_pos_workspace_bytes(B, cin, cout))
-                L.call('vv_conv3d_k4s2_pos_fwd', L.ptr(x), L.ptr(wsk), None, None, L.ptr(y), B, side, cin, cout, 0, dt, L.ptr(ws), ws.numel(), st)
-            else:
-                L.call('vv_conv3d_k4s2_skip_fwd', L.ptr(x), L.ptr(wsk), None, None, L.ptr(y), B, side, cin, cout, 0, dt, st)
-            return y
-        if wp is None:
-            wp = self._aempty(cout, 64 * cin)
-            L.call('vv_pack_conv_k4', L.ptr(w_keras), L.ptr(wp), cin, cout, dt, st)
-        if L.load().vv_conv3d_k4s2_direct_supported(side, cin, cout, dt):
-            L.call('vv_conv3d_k4s2_direct_fwd', L.ptr(x), L.ptr(wp), None, None, L.ptr(y), B, side, cin, cout, 0, dt, st)
+    def _route(self, direction, side, cin, cout):
+        if direction == R.CONV:
+            return R.conv_route(side, cin, cout, self.dt, False, False, True, self.sw)
+        return R.convT_route(side, cin, cout, self.dt, False, False, self.sw)
+
+    @staticmethod
+    def _batched(route, layer):
+        """True when this launch reads an image of the step's batched pack (_prepack): the 'pos' / 'skip' forms always (an engine holds
+        their images only after an evaluation pack, and the weights change every step), 'whole' as a data gradient (the forward
+        layer reads the engine's image)."""
+        return route in ('pos', 'skip') or (route == 'whole' and layer is None)
+
+    def _stride2(self, direction, x, w_keras, B, side, cin, cout, layer=None):
+        """Stride-2 layer of x [B,side^3,cin] with a Keras kernel array, raw output (no scale / shift / activation: BatchNorm follows
+        with batch statistics).  layer: the engine's plan record of a forward layer; None for a data gradient.  The weight image is the
+        step's batched one, the engine's, or packed here."""
+        route = self._route(direction, side, cin, cout)
+        kind = R.ROUTE_IMAGE[direction][route]
+        if self._batched(route, layer):
+            w = self._prepacked.get((direction, w_keras.data_ptr(), cin, cout))
         else:
-            ws = self.ws.get(L.load().vv_conv3d_k4s2_workspace_bytes(B, side, cin, cout, dt))
-            L.call('vv_conv3d_k4s2_fwd', L.ptr(x), L.ptr(wp), None, None, L.ptr(y), B, side, cin, cout, 0, dt, L.ptr(ws), ws.numel(), st)
+            w = layer.images.get(kind) if layer is not None else None
+        if w is None:
+            w = R.pack_image(direction, kind, w_keras, cin, cout, self.dt, _st())
+        o = side // 2 if direction == R.CONV else 2 * side
+        y = self._aempty(B, o, o, o, cout)
+        (R.launch_conv if direction == R.CONV else R.launch_convT)(L.call, route, self.ws, x, w, None, None, y, B, side, cin, cout, 0, self.dt, None, _st())
         return y
 
-    def _convT(self, x, w_keras, B, side, cin, cout, packed=None, packed_frag=None, packed_whole=None):
-        """Conv3DTranspose k4 s2 of x [B,side^3,cin] with a Keras kernel array read as [4,4,4,cout,cin]: the forward
-        transposed layers (packed / packed_frag = the engine's images) and the data gradients of the strided convolutions."""
-        dt, st = self.dt, _st()
-        y = self._aempty(B, 2 * side, 2 * side, 2 * side, cout)
-        lib = L.load()
-        if not os.environ.get('VV_NO_SKIP') and (lib.vv_convT3d_k4s2_skip_supported(side, cin, cout, dt) or lib.vv_convT3d_k4s2_pos_supported(side, cin, cout, dt)):
-            wsk = getattr(self, '_prepacked', {}).get((1, w_keras.data_ptr(), cin, cout))     # 4^3 -> 8^3 / 2^3 -> 4^3 (bf16): see _conv
-            if wsk is None:
-                wsk = self._aempty(64 * cin * cout)
-                L.call('vv_pack_convT_k4s2_skip', L.ptr(w_keras), L.ptr(wsk), cin, cout, st)
-            if side == 2:
-                ws = self.ws.get(lib.vv_convT3d_k4s2_pos_workspace_bytes(B, cin, cout))
-                L.call('vv_convT3d_k4s2_pos_fwd', L.ptr(x), L.ptr(wsk), None, None, L.ptr(y), B, side, cin, cout, 0, dt, L.ptr(ws), ws.numel(), st)
-            else:
-                L.call('vv_convT3d_k4s2_skip_fwd', L.ptr(x), L.ptr(wsk), None, None, L.ptr(y), B, side, cin, cout, 0, dt, st)
-            return y
-        if (L.load().vv_convT3d_k4s2_whole_supported(side, cin, cout, dt) and not os.environ.get('VV_NO_DIRECT')
-                and not os.environ.get('VV_NO_WHOLE')):
-            # 8^3 x 128 -> 16^3 x 64 (the widest decoder layer forward, and the data gradient of the widest encoder layer):
-            # whole-sample kernel; its weight image is packed here (the weights change every step)
-            wk = packed_whole                        # the forward layer: the engine's image; a data gradient: the step's prepacked one
-            if wk is None:
-                wk = getattr(self, '_prepacked', {}).get((1, w_keras.data_ptr(), cin, cout))
-            if wk is None:
-                wk = self._aempty(64 * cin * cout)
-                L.call('vv_pack_convT_k4s2_skip', L.ptr(w_keras), L.ptr(wk), cin, cout, st)
-            L.call('vv_convT3d_k4s2_whole_fwd', L.ptr(x), L.ptr(wk), None, None, L.ptr(y), B, side, cin, cout, 0, dt, st)
-        elif L.load().vv_convT3d_k4s2_direct_supported(side, cin, cout, dt) and not os.environ.get('VV_NO_DIRECT'):
-            wf = packed_frag
-            if wf is None:
-                wf = self._aempty(64 * cin * cout)
-                L.call('vv_pack_convT_k4s2_frag', L.ptr(w_keras), L.ptr(wf), cin, cout, st)
-            L.call('vv_convT3d_k4s2_direct_fwd', L.ptr(x), L.ptr(wf), None, None, L.ptr(y), B, side, cin, cout, 0, dt, st)
-        else:
-            wp = packed
-            if wp is None:
-                wp = self._aempty(8, cout, 8 * cin)
-                L.call('vv_pack_convT_k4s2', L.ptr(w_keras), L.ptr(wp), cin, cout, dt, st)
-            ws = self.ws.get(L.load().vv_convT3d_k4s2_workspace_bytes(B, side, cin, cout, dt))
-            L.call('vv_convT3d_k4s2_fwd', L.ptr(x), L.ptr(wp), None, None, L.ptr(y), B, side, cin, cout, 0, dt, L.ptr(ws), ws.numel(), st)
-        return y
+    def _conv(self, x, w_keras, B, side, cin, cout, layer=None):
+        """Conv3D k4 s2 with a Keras kernel array read as [4,4,4,cin,cout]: the forward layers and the data gradients of the
+        transposed layers."""
+        return self._stride2(R.CONV, x, w_keras, B, side, cin, cout, layer)
+
+    def _convT(self, x, w_keras, B, side, cin, cout, layer=None):
+        """Conv3DTranspose k4 s2 with a Keras kernel array read as [4,4,4,cout,cin]: the forward transposed layers and the data gradients
+        of the strided convolutions (8^3 x 128 -> 16^3 x 64 is both the widest decoder layer and the data gradient of the widest
+        encoder layer)."""
+        return self._stride2(R.CONVT, x, w_keras, B, side, cin, cout, layer)
 
     # ------------------------------------------------------------------ one step
     def step(self, x, y, eps=None, drop_mask=None, drop_scale=1.0):
         """x, y: float32 CUDA [B,D,D,D,1].  Returns device tensors (loss_kl or None, stats [B,4], metrics [4])."""
-        self.enc.ensure_packed(fold=False)
-        self.dec.ensure_packed(fold=False)      # (packing the decoder on a side stream under the encoder's forward was measured: +0.11 ms per step)
-        self.grads.begin_step()
-        self._set_producer_streams()
-        self._prepack()
+        self._begin(self.enc, self.dec, step=True)   # (packing the decoder on a side stream under the encoder's forward was measured: +0.11 ms per step)
         B = x.shape[0]
         inv_gb = 1.0 / float(B * self.world)      # loss scaled by the GLOBAL batch (AE3D.py:46-48)
         enc_out, est = self._encoder_forward(x, B)
@@ -473,40 +441,31 @@ class Trainer:
         return kl, stats, metrics
 
     def _prepack(self):
-        """Every skip / position / whole-sample weight image the step will ask for (forward layers and data gradients: nine at the 32^3
-        model), packed by ONE vv_pack_skip_images call = two launches, instead of nine 5-8 us launches spread over the step.  _conv /
-        _convT look the images up by (kind, weight pointer, cin, cout) and pack per use when they find none (other entry points).  The
-        images are dropped again when Adam has moved the weights (_apply)."""
+        """Every 'skip' weight image (position-major, skip and whole-sample forms) the step will ask for and no engine holds (forward
+        layers and data gradients: nine at the 32^3 model), packed by ONE vv_pack_skip_images call = two launches, instead of nine 5-8 us
+        launches spread over the step.  _stride2 looks them up by (direction, weight pointer, cin, cout) and packs per use when it finds
+        none (other entry points).  The images are dropped again when Adam has moved the weights (_apply)."""
         self._prepacked = {}
-        if self.dt != L.VV_BF16 or os.environ.get('VV_NO_SKIP') or os.environ.get('VV_NO_PREPACK'):
+        if self.dt != L.VV_BF16 or self.sw.no_skip or self.sw.no_prepack:
             return
-        lib, dt = L.load(), self.dt
-        jobs = []                                                     # (kind, weight tensor, cin, cout)
+        jobs = []                                                     # (direction, weight tensor, cin, cout)
 
-        def conv_ok(side, cin, cout):
-            return side >= 2 and (lib.vv_conv3d_k4s2_skip_supported(side, cin, cout, dt) or lib.vv_conv3d_k4s2_pos_supported(side, cin, cout, dt))
-
-        def convT_ok(side, cin, cout, whole):
-            if side >= 1 and (lib.vv_convT3d_k4s2_skip_supported(side, cin, cout, dt) or lib.vv_convT3d_k4s2_pos_supported(side, cin, cout, dt)):
-                return True
-            return bool(whole and lib.vv_convT3d_k4s2_whole_supported(side, cin, cout, dt) and not os.environ.get('VV_NO_DIRECT') and not os.environ.get('VV_NO_WHOLE'))
+        def job(direction, layer, w, side, cin, cout):
+            if self._batched(self._route(direction, side, cin, cout), layer):
+                jobs.append((direction, w, cin, cout))
 
         if self.enc is not None:
             fe, side = self.enc.filters, self.enc.D // 2
-            for i in range(1, len(fe) - 1):
+            for i, ly in enumerate(self.enc.plan, 1):
                 w = self.enc.params['conv%d/kernel' % i]
-                if conv_ok(side, fe[i - 1], fe[i]):
-                    jobs.append((0, w, fe[i - 1], fe[i]))             # the forward layer
-                if convT_ok(side // 2, fe[i], fe[i - 1], True):
-                    jobs.append((1, w, fe[i], fe[i - 1]))             # its data gradient (a transposed convolution with the same array)
+                job(R.CONV, ly, w, side, fe[i - 1], fe[i])            # the forward layer
+                job(R.CONVT, None, w, side // 2, fe[i], fe[i - 1])    # its data gradient (a transposed convolution with the same array)
                 side //= 2
         fd, side = self.dec.filters, self.dec.S
-        for i in range(1, len(fd) - 1):
+        for i, ly in enumerate(self.dec.plan, 1):
             w = self.dec.params['convT%d/kernel' % i]
-            if convT_ok(side, fd[i - 1], fd[i], False):
-                jobs.append((1, w, fd[i - 1], fd[i]))                 # the forward layer (the whole-sample layer uses the engine's image)
-            if conv_ok(2 * side, fd[i], fd[i - 1]):
-                jobs.append((0, w, fd[i], fd[i - 1]))                 # its data gradient
+            job(R.CONVT, ly, w, side, fd[i - 1], fd[i])               # the forward layer (the whole-sample layer uses the engine's image)
+            job(R.CONV, None, w, 2 * side, fd[i], fd[i - 1])          # its data gradient
             side *= 2
         if not jobs:
             return
@@ -523,23 +482,16 @@ class Trainer:
 
     def _join_wgrad(self):
         """The launch stream waits for the weight-gradient stream: every weight gradient is in its bucket."""
-        if getattr(self, 'wgrad_stream', None) is not None and self._side_used:
+        if self.wgrad_stream is not None and self._side_used:
             torch.cuda.current_stream(self.dev).wait_stream(self.wgrad_stream)
             self._side_used = False
-
-    def _set_producer_streams(self):
-        if getattr(self, 'wgrad_stream', None) is not None:
-            self.grads.producer_streams = (torch.cuda.current_stream(self.dev), self.wgrad_stream)
 
     def step_from_latent(self, enc_out, y, eps=None, drop_mask=None, drop_scale=1.0, l2=0.0):
         """Decoder-only step for the image -> 3D model (nolbo.py:786-833): enc_out [B, 2L] (mean | logVar) comes from a 2D
         encoder owned by the caller.  Trains the decoder and returns (loss_kl, stats, metrics, d total / d enc_out) so the
         caller can continue the backward pass through its own encoder.  l2: coefficient of the decoder's kernel / bias
         regularisers when the caller's loss includes them."""
-        self.dec.ensure_packed(fold=False)
-        self.grads.begin_step()
-        self._set_producer_streams()
-        self._prepack()
+        self._begin(self.dec, step=True)
         overlap, self.overlap = self.overlap, self.overlap and l2 == 0      # the l2 terms are added before the cross-rank sum
         B = enc_out.shape[0]
         inv_gb = 1.0 / float(B * self.world)
@@ -561,11 +513,7 @@ class Trainer:
         graph to enc_out (continuing into the HIP encoder backward) and to whatever parameters latent_fn touched."""
         if self.var:
             raise ValueError('step_custom_latent expects a Trainer built with variational=False (the decoder input is z_input)')
-        self.enc.ensure_packed(fold=False)
-        self.dec.ensure_packed(fold=False)
-        self.grads.begin_step()
-        self._set_producer_streams()
-        self._prepack()
+        self._begin(self.enc, self.dec, step=True)
         B = x.shape[0]
         inv_gb = 1.0 / float(B * self.world)
         enc_out, est = self._encoder_forward(x, B)
@@ -579,7 +527,7 @@ class Trainer:
         return stats, metrics, aux
 
     def _encoder_forward(self, x, B):
-        if getattr(self.enc, 'pool_max', False) or getattr(self.enc, 'pool_none', False) or getattr(self.enc, 'final_sigmoid', False):
+        if self.enc.pool_max or self.enc.pool_none or self.enc.final_sigmoid:
             raise NotImplementedError("training-mode forward with final_pool='max' / 'None' or an encoder final_activation")
         enc, st, dt = self.enc, _st(), self.dt
         D, fe, act = enc.D, enc.filters, enc.act
@@ -590,8 +538,8 @@ class Trainer:
         L.call('vv_conv3d_first_fwd', L.ptr(x), L.ptr(enc.packed['w0']), None, None, L.ptr(c), B, D, fe[0], 0, dt, st)
         h, bn = self._bn_fwd(c, B * side ** 3, fe[0], enc, 'bn0', act)
         ec.append(c); eh.append(h); ebn.append(bn)
-        for i in range(1, len(fe) - 1):
-            c = self._conv(eh[-1], enc.params['conv%d/kernel' % i], B, side, fe[i - 1], fe[i], packed=enc.packed['w%d' % i])
+        for i, ly in enumerate(enc.plan, 1):
+            c = self._conv(eh[-1], enc.params['conv%d/kernel' % i], B, side, fe[i - 1], fe[i], layer=ly)
             side //= 2
             h, bn = self._bn_fwd(c, B * side ** 3, fe[i], enc, 'bn%d' % i, act)
             ec.append(c); eh.append(h); ebn.append(bn)
@@ -619,8 +567,7 @@ class Trainer:
         1463, 1496): BatchNorm normalises with the batch statistics and updates its moving statistics, nothing else changes.
         z_fn(z float32 [B,L]) -> z may edit the latent before the decoder (missing-latent masking).
         Returns (z, kl or None, probs, stats [B,4], metrics [4])."""
-        self.enc.ensure_packed(fold=False)
-        self.dec.ensure_packed(fold=False)
+        self._begin(self.enc, self.dec)
         B = x.shape[0]
         enc_out, _ = self._encoder_forward(x, B)
         z, z_act, kl, _ = self._latent(enc_out, eps, None, 1.0, B)
@@ -628,29 +575,22 @@ class Trainer:
             z = z_fn(z)
             z_act = self._cast(z)
         fw = self._decoder_forward(z_act, y, B)
-        self._moved_statistics(self.enc, self.dec)
+        self.enc.statistics_moved()
+        self.dec.statistics_moved()
         return z, kl, fw['probs'], fw['stats'], fw['metrics']
 
     def decoder_training_mode(self, z, y):
         """Decoder half of forward_training_mode for an edited latent (the corrected pass of getEval)."""
-        self.dec.ensure_packed(fold=False)
+        self._begin(self.dec)
         fw = self._decoder_forward(self._cast(z), y, z.shape[0])
-        self._moved_statistics(self.dec)
+        self.dec.statistics_moved()
         return fw['probs'], fw['stats'], fw['metrics']
 
     def _latent_decoder(self, enc_out, y, eps, drop_mask, drop_scale, B, inv_gb):
-        dec, dev, st, dt = self.dec, self.dev, _st(), self.dt
-        D, fd, act = dec.D, dec.filters, dec.act
-        Lz = dec.L
         z, z_act, kl, eps = self._latent(enc_out, eps, drop_mask, drop_scale, B)
         fw = self._decoder_forward(z_act, y, B)
-        S, ch = dec.S, dec.ch
-        lin, n1 = S ** 3 * ch, S ** 3 * fd[0]
-        c_d0, t0, bn_d0, c_d1, bn_d1 = fw['c_d0'], fw['t0'], fw['bn_d0'], fw['c_d1'], fw['bn_d1']
-        dc_, dh_, dbn, probs, stats, metrics, side = fw['dc_'], fw['dh_'], fw['dbn'], fw['probs'], fw['stats'], fw['metrics'], fw['side']
-        nd = len(fd) - 1
-        w5 = dec.params['convT%d/kernel' % nd]
-        return self._decoder_backward_rest(locals())
+        de = self._decoder_backward(fw, y, enc_out, eps, z, z_act, drop_mask, drop_scale, B, inv_gb)
+        return kl, fw['stats'], fw['metrics'], de
 
     def _decoder_forward(self, z_act, y, B):
         dec, dev, st, dt = self.dec, self.dev, _st(), self.dt
@@ -666,22 +606,18 @@ class Trainer:
         h_d1, bn_d1 = self._bn_fwd(c_d1, B * S ** 3, fd[0], dec, 'bnT0', act)
         dc_, dh_, dbn = [c_d1], [h_d1], [bn_d1]
         side = S
-        lib = L.load()
-        for i in range(1, len(fd) - 1):
-            ww = dec.packed.get('ww%d' % i)
-            if (ww is not None and not os.environ.get('VV_NO_STATS_FUSION') and not os.environ.get('VV_NO_WHOLE') and not os.environ.get('VV_NO_DIRECT')
-                    and lib.vv_convT3d_k4s2_whole_supported(side, fd[i - 1], fd[i], dt)):
+        for i, ly in enumerate(dec.plan, 1):
+            if self._route(R.CONVT, side, fd[i - 1], fd[i]) == 'whole' and not self.sw.no_stats_fusion:
                 # the widest decoder layer: its kernel leaves the column sums of its own output (no statistics sweep over 134 MB)
                 c = self._aempty(B, 2 * side, 2 * side, 2 * side, fd[i])
-                nblk = lib.vv_convT3d_k4s2_whole_stats_blocks(B)
+                nblk = L.load().vv_convT3d_k4s2_whole_stats_blocks(B)
                 part = self._empty(nblk * 2 * fd[i])
-                L.call('vv_convT3d_k4s2_whole_stats_fwd', L.ptr(dh_[-1]), L.ptr(ww), L.ptr(c), L.ptr(part), part.numel() * 4, B, side, fd[i - 1], fd[i],
+                L.call('vv_convT3d_k4s2_whole_stats_fwd', L.ptr(dh_[-1]), L.ptr(ly.images['skip']), L.ptr(c), L.ptr(part), part.numel() * 4, B, side, fd[i - 1], fd[i],
                        dt, st)
                 side *= 2
-                h, bn = self._bn_fwd_from_partials(c, part, nblk, B * side ** 3, fd[i], dec, 'bnT%d' % i, act)
+                h, bn = self._bn_fwd(c, B * side ** 3, fd[i], dec, 'bnT%d' % i, act, part, nblk)
             else:
-                c = self._convT(dh_[-1], dec.params['convT%d/kernel' % i], B, side, fd[i - 1], fd[i], packed=dec.packed['w%d' % i],
-                                packed_frag=dec.packed.get('wf%d' % i), packed_whole=ww)
+                c = self._convT(dh_[-1], dec.params['convT%d/kernel' % i], B, side, fd[i - 1], fd[i], layer=ly)
                 side *= 2
                 h, bn = self._bn_fwd(c, B * side ** 3, fd[i], dec, 'bnT%d' % i, act)
             dc_.append(c); dh_.append(h); dbn.append(bn)
@@ -696,14 +632,14 @@ class Trainer:
         return {'c_d0': c_d0, 't0': t0, 'bn_d0': bn_d0, 'c_d1': c_d1, 'bn_d1': bn_d1, 'dc_': dc_, 'dh_': dh_, 'dbn': dbn, 'probs': probs,
                 'stats': stats, 'metrics': metrics, 'side': side}
 
-    def _decoder_backward_rest(self, fwd):
-        """Backward half of _latent_decoder; `fwd` = its locals (forward intermediates)."""
-        dec, dev, st, dt = self.dec, self.dev, _st(), self.dt
-        D, fd, act = dec.D, dec.filters, dec.act
-        B, y, inv_gb, enc_out, eps, z, z_act, kl = (fwd[k] for k in ('B', 'y', 'inv_gb', 'enc_out', 'eps', 'z', 'z_act', 'kl'))
-        drop_mask, drop_scale, Lz, S, ch, lin, n1, nd, w5 = (fwd[k] for k in ('drop_mask', 'drop_scale', 'Lz', 'S', 'ch', 'lin', 'n1', 'nd', 'w5'))
-        c_d0, t0, bn_d0, c_d1, bn_d1 = (fwd[k] for k in ('c_d0', 't0', 'bn_d0', 'c_d1', 'bn_d1'))
-        dc_, dh_, dbn, probs, stats, metrics, side = (fwd[k] for k in ('dc_', 'dh_', 'dbn', 'probs', 'stats', 'metrics', 'side'))
+    def _decoder_backward(self, fw, y, enc_out, eps, z, z_act, drop_mask, drop_scale, B, inv_gb):
+        """Backward half of _latent_decoder; fw = what _decoder_forward returned.  -> d loss / d enc_out."""
+        dec, st, dt = self.dec, _st(), self.dt
+        D, fd, act, Lz, S, ch = dec.D, dec.filters, dec.act, dec.L, dec.S, dec.ch
+        lin, n1, nd = S ** 3 * ch, S ** 3 * fd[0], len(fd) - 1
+        w5 = dec.params['convT%d/kernel' % nd]
+        c_d0, t0, bn_d0, c_d1, bn_d1 = fw['c_d0'], fw['t0'], fw['bn_d0'], fw['c_d1'], fw['bn_d1']
+        dc_, dh_, dbn, probs, side = fw['dc_'], fw['dh_'], fw['dbn'], fw['probs'], fw['side']
         # ---------------- backward: decoder tail
         dlogit = self._empty(B, D, D, D, 1)
         L.call('vv_bce_bwd', L.ptr(probs), L.ptr(y), L.ptr(dlogit), B, D ** 3, 0.6, 1e-7, inv_gb, st)
@@ -746,7 +682,7 @@ class Trainer:
         if self.debug is not None:
             self.debug.update({'dlogit': dlogit, 'probs': probs, 'enc_out': enc_out, 'z': z, 'dz': dz, 'de': de, 'c_d0': c_d0, 'dcv0': dcv0,
                                't0': t0, 'dt0': dt0, 'h_dec': dh_, 'c_dec': dc_})
-        return kl, stats, metrics, de
+        return de
 
     def _encoder_backward(self, x, de, est, B):
         enc, st = self.enc, _st()
@@ -785,7 +721,7 @@ class Trainer:
         lr_t = self.lr * (1.0 - ADAM_B2 ** self.t) ** 0.5 / (1.0 - ADAM_B1 ** self.t)
         # one launch for all variables: a device table of <= 16384-element chunks, rebuilt only when a tensor moved
         ptrs = tuple(self._p(name).data_ptr() for name, _ in self.order)
-        if getattr(self, '_adam_ptrs', None) != ptrs:
+        if self._adam_ptrs != ptrs:
             recs = []
             for name, _ in self.order:
                 p, g, m, v = self._p(name), self._g(name), self.m[name], self.v[name]
@@ -795,6 +731,6 @@ class Trainer:
             self._adam_table = torch.from_numpy(np.asarray(recs, dtype=np.int64)).to(self.dev)
             self._adam_ptrs = ptrs
         L.call('vv_adam_step_multi', L.ptr(self._adam_table), self._adam_table.shape[0], lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, st)
-        if self.enc is not None:
-            self.enc._dirty = True
-        self.dec._dirty = True
+        for e in (self.enc, self.dec):
+            if e is not None:
+                e.weights_changed()

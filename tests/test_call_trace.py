@@ -1,0 +1,248 @@
+"""Which library calls the engines and the trainer issue, in which order and with which arguments, pinned for every configuration
+the kernel-form policy (voxvae/routes.py) distinguishes.  CPU only: four names are replaced so that nothing touches a device --
+
+    lib.call                                   appends [name, *args] to the trace instead of calling
+    lib.ptr                                    returns a c_void_p that remembers dtype and shape of its tensor
+    engine._require_gpu / ._stream, train._st  no device, stream 0
+    engine._Workspace.get                      a CPU byte tensor
+
+-- while lib.load() stays real: the `*_supported` / `*_workspace_bytes` functions are host code.  tests/golden/call_traces.json was
+recorded by this recorder from the commit BEFORE the route module existed (same four replacements).  It holds every distinct call once
+and each case as the sequence of their names, and changes only with a deliberate route change:
+    python tests/test_call_trace.py --write [--package DIR]        (DIR: another checkout's anytime-3d-reconstruction_amd)
+"""
+import contextlib
+import ctypes
+import functools
+import glob
+import hashlib
+import json
+import os
+import re
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'call_traces.json')
+LATENT = 64
+SWITCHES = ('VV_NO_SKIP', 'VV_NO_DIRECT', 'VV_NO_WHOLE', 'VV_NO_LATENT_TAIL', 'VV_NO_POS_TAIL', 'VV_NO_PREPACK', 'VV_NO_STATS_FUSION',
+            'VV_FP8_E2', 'VV_FP8_LAST', 'VV_FP8_D5', 'VV_FP8_OFF', 'VV_FP8_SHAPED')
+
+
+def _cases():
+    """name -> dict(mode, side, dtype, policy, env, batch, variational, pool)."""
+    cases = {}
+
+    def add(mode, side, dtype, policy=None, env=None, batch=8, variational=True, pool='average'):
+        name = '%s-%d-%s' % (mode, side, dtype + ('.' + policy if policy else ''))
+        name += ''.join('-%s=%s' % kv for kv in sorted((env or {}).items())) + ('' if variational else '-ae') + ('' if pool == 'average' else '-pool' + pool)
+        assert name not in cases
+        cases[name] = dict(mode=mode, side=side, dtype=dtype, policy=policy, env=env or {}, batch=batch, variational=variational, pool=pool)
+
+    for side in (16, 32, 64):
+        for mode in ('eval', 'tail', 'train'):
+            for dtype in ('f32', 'bf16'):
+                add(mode, side, dtype)
+            if mode != 'train':
+                for policy in ('wide', 'mid', 'most', 'all'):
+                    add(mode, side, 'fp8', policy)
+    for sw in SWITCHES[:7]:
+        for mode in ('eval', 'tail', 'train'):
+            add(mode, 32, 'bf16', env={sw: '1'})
+    for policy in ('wide', 'mid'):
+        for env in ({'VV_FP8_E2': '0'}, {'VV_FP8_E2': 'igemm'}, {'VV_FP8_LAST': '0'}, {'VV_FP8_LAST': 'igemm'}, {'VV_FP8_D5': '1'}, {'VV_FP8_OFF': 'E3,D3'}):
+            add('eval', 32, 'fp8', policy, env=env, batch=256)      # VV_FP8_D5 needs B * (side / 4)^2 >= 128
+    for mode in ('eval', 'tail', 'train'):
+        add(mode, 32, 'bf16', variational=False)
+    for dtype in ('f32', 'bf16'):
+        add('train_decoder_only', 32, dtype)
+        add('forward_only', 32, dtype)
+        add('forward_training_mode', 32, dtype)
+        for pool in ('max', 'None'):
+            add('eval', 32, dtype, pool=pool)
+    return cases
+
+
+CASES = _cases()
+
+
+class _Ptr(ctypes.c_void_p):
+    """What the replaced lib.ptr returns: a null pointer that knows what it stands for."""
+
+
+def _render(a):
+    if a is None:
+        return 'None'
+    if isinstance(a, _Ptr):
+        return a.what
+    if isinstance(a, ctypes.c_void_p):
+        return 'stream'
+    if isinstance(a, ctypes.Array):
+        return '[%s]' % ', '.join('ptr' if a._type_ is ctypes.c_void_p else str(v) for v in a)
+    if isinstance(a, float):
+        return a.hex()
+    if isinstance(a, bool):
+        raise TypeError('bool passed to the C ABI')
+    if isinstance(a, int):
+        return str(a)
+    raise TypeError('unexpected argument %r' % (a,))
+
+
+@contextlib.contextmanager
+def _recording(trace):
+    import torch
+    from voxvae import engine as E, lib as L, train as T
+
+    def ptr(t):
+        if t is None:
+            return None
+        p = _Ptr(0)
+        p.what = '%s%s' % (str(t.dtype).replace('torch.', ''), list(t.shape))
+        return p
+
+    saved = [(L, 'call', L.call), (L, 'ptr', L.ptr), (E, '_require_gpu', E._require_gpu), (E, '_stream', E._stream), (T, '_st', T._st),
+             (E._Workspace, 'get', E._Workspace.get)]
+    L.call = lambda name, *args: trace.append('%s(%s)' % (name, ', '.join(_render(a) for a in args)))
+    L.ptr = ptr
+    E._require_gpu = lambda: None
+    E._stream = T._st = lambda: ctypes.c_void_p(0)
+    E._Workspace.get = lambda self, nbytes: torch.empty(max(int(nbytes), 16), dtype=torch.uint8)
+    try:
+        yield
+    finally:
+        for obj, name, value in saved:
+            setattr(obj, name, value)
+
+
+def _zeros(engine):
+    import torch
+    engine.set_params({k: torch.zeros(s) for k, s in engine.param_shapes().items()})
+    return engine
+
+
+def record(case):
+    """The trace of one case: a list of 'name(arg, ...)' strings, with '# ...' lines where the driver reports a decision."""
+    import torch
+    import voxvae
+    from voxvae import engine as E, lib as L, synthetic as syn, train as T
+    c = case
+    cfg = syn.make_config(c['side'], LATENT, c['variational'])
+    cfg['encoder']['final_pool'] = c['pool']
+    saved_env = {k: os.environ.get(k) for k in SWITCHES}
+    saved_policy = voxvae.fp8_policy()
+    trace = []
+    try:
+        for k in SWITCHES:
+            os.environ.pop(k, None)
+        os.environ.update(c['env'])
+        if c['policy']:
+            voxvae.set_fp8_policy(c['policy'])
+        with _recording(trace):
+            enc = _zeros(E.EncoderEngine(cfg['encoder'], c['dtype'], 'cpu'))
+            dec = _zeros(E.DecoderEngine(cfg['decoder'], c['dtype'], 'cpu'))
+            B, D, var = c['batch'], c['side'], c['variational']
+            x = torch.zeros(B, D, D, D, 1)
+            eps = torch.zeros(B, LATENT)
+            mode = c['mode']
+            if mode == 'eval':
+                out = enc.forward(x)
+                if c['pool'] == 'average':
+                    z_act = E.reparam_kl(out, eps, LATENT, enc.dt)[1] if var else out.to(enc.tdt)
+                    dec.forward(z_act, x, want_metrics=True)
+            elif mode == 'tail':
+                lt, pt = E.latent_tail_supported(enc, dec, var), E.pos_latent_tail_supported(enc, dec, var, batch=B)
+                trace.append('# latent_tail_supported=%s pos_latent_tail_supported=%s' % (bool(lt), bool(pt)))
+                if lt:
+                    h = enc.forward(x, stop_before_tail=True, stop_before_pos=bool(pt))
+                    h1 = E.latent_tail(enc, dec, h, eps, var, want_enc_out=True, pos_layer=bool(pt))[4]
+                    dec.forward(None, x, h1=h1)
+            elif mode == 'train':
+                tr = T.Trainer(enc, dec, variational=var)
+                for _ in range(2):
+                    tr.step(x, x, eps=eps if var else None)
+                    trace.append('# end of step')
+                enc.forward(x)
+            elif mode == 'train_decoder_only':
+                tr = T.Trainer(None, dec, variational=True)
+                tr.step_from_latent(torch.zeros(B, 2 * LATENT), x, eps=eps)
+            elif mode == 'forward_only':
+                T.Trainer.forward_only(enc=enc).encoder_training_mode(x)
+                trace.append('# decoder')
+                T.Trainer.forward_only(dec=dec).decoder_training_mode(torch.zeros(B, LATENT), x)
+            elif mode == 'forward_training_mode':
+                T.Trainer(enc, dec, variational=var).forward_training_mode(x, x, eps=eps)
+            else:
+                raise ValueError(mode)
+    finally:
+        voxvae.set_fp8_policy(saved_policy)
+        for k, v in saved_env.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    return trace
+
+
+def _call_id(call, taken):
+    """A short stable name for one call string: its entry point and as much of the string's SHA-1 as keeps it unique."""
+    name, digest = re.match(r'(?:vv_)?(\w*)', call).group(1), hashlib.sha1(call.encode()).hexdigest()
+    n = 4
+    while taken.get('%s#%s' % (name, digest[:n]), call) != call:
+        n += 1
+    return '%s#%s' % (name, digest[:n])
+
+
+def _store(traces):
+    """The golden file: every distinct call once ('calls': id -> call, one per line), every case as the sequence of its ids."""
+    calls, ids = {}, {}
+    for name in sorted(traces):
+        for call in traces[name]:
+            if call not in ids:
+                ids[call] = _call_id(call, calls)
+                calls[ids[call]] = call
+    return {'calls': calls, 'traces': {name: ' '.join(ids[c] for c in t) for name, t in traces.items()}}
+
+
+@functools.lru_cache(maxsize=None)
+def _golden():
+    with open(GOLDEN) as f:
+        g = json.load(f)
+    return {name: [g['calls'][i] for i in t.split()] for name, t in g['traces'].items()}
+
+
+def test_golden_covers_exactly_the_cases():
+    assert sorted(_golden()) == sorted(CASES)
+
+
+@pytest.mark.parametrize('name', sorted(CASES))
+def test_call_trace(name):
+    want, got = _golden()[name], record(CASES[name])
+    for i, (w, g) in enumerate(zip(want, got)):
+        assert w == g, '%s: call %d differs\n  recorded from the parent: %s\n  now:                      %s' % (name, i, w, g)
+    assert len(want) == len(got), '%s: %d calls recorded from the parent, %d now; first extra: %s' % (
+        name, len(want), len(got), (want + got)[min(len(want), len(got))])
+
+
+def test_switches_are_named_in_the_route_module_only():
+    pkg = os.path.join(ROOT, 'anytime-3d-reconstruction_amd', 'voxvae')
+    with open(os.path.join(ROOT, 'INTEGRATION.md')) as f:
+        doc = f.read()
+    for sw in SWITCHES:
+        users = sorted(os.path.basename(p) for p in glob.glob(os.path.join(pkg, '*.py')) if re.search(r'\b%s\b' % sw, open(p).read()))
+        assert users == ['routes.py'], (sw, users)
+        assert re.search(r'\b%s\b' % sw, doc), '%s is not documented in INTEGRATION.md' % sw
+
+
+if __name__ == '__main__':
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--write', action='store_true', required=True)
+    ap.add_argument('--package', default=os.path.join(ROOT, 'anytime-3d-reconstruction_amd'))
+    a = ap.parse_args()
+    sys.path.insert(0, a.package)
+    traces = {name: record(CASES[name]) for name in sorted(CASES)}
+    with open(GOLDEN, 'w') as f:
+        json.dump(_store(traces), f, indent=0, sort_keys=True)
+        f.write('\n')
+    print('%d cases, %d calls -> %s' % (len(traces), sum(len(t) for t in traces.values()), GOLDEN))
