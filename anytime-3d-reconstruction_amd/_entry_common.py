@@ -2,6 +2,7 @@
 (test_modelnet_VAE.py:169-192, train_modelnet_category_VAE.py:109-132) with the voxel side as a parameter, and the
 argparse overrides SURVEY §5 asks for (--voxel, --batch, --dtype, --synthetic ...)."""
 import argparse
+import os
 
 
 def make_config(latent_dim=64, voxel=64, variational=True):
@@ -48,7 +49,46 @@ def parse(description, train=False):
     ap.add_argument('--packed-data', action='store_true', help='host loader that keeps the split as bits and serves PackedVoxels batches (1 bit per voxel over PCIe)')
     ap.add_argument('--pipeline', type=int, default=1, help='test_modelnet_VAE.py: batches in flight (voxvae.streams.HostPipeline); 1 = the reference\'s synchronous loop')
     ap.add_argument('--dump-dir', default=None, help='test_modelnet_VAE.py: save <missing_pr>_cl_label/_gt/_pred.npy here (reference :159-165)')
-    return ap.parse_args()
+    ap.add_argument('--sampling', type=int, default=0, help='test_modelnet_VAE.py only: also score the sampled-mean reconstruction over this many latents per object (0 = off); needs --pipeline 1')
+    a = ap.parse_args()
+    if a.sampling:
+        # one script owns the option: elsewhere (train + test getEval in one loop, other model classes) its numbers would mean something else
+        if os.path.basename(sys.argv[0]) != SAMPLING_SCRIPT:
+            ap.error('--sampling is an option of %s' % SAMPLING_SCRIPT)
+        if a.sampling < 0:
+            ap.error('--sampling must be >= 0')
+        if a.pipeline > 1:
+            ap.error('--sampling scores every batch synchronously: use --pipeline 1')
+        score_sampled_mean(a.sampling)
+    return a
+
+
+# --sampling K of test_modelnet_VAE.py.  That script is a fixed point of this repository (it is not edited), and its loop is
+# getEval -> RunningMeans.add -> Progress.show with the model and the batch out of this module's reach, so the option is served from here:
+# every getEval of the model classes is followed, for the same (input, target) pair, by getSampledEval over K latents per object (the
+# reference's nolbo_test.py:167-180), and Progress.show appends the running means of its loss / pr / rc as sloss / spr / src.
+# getEval's own result is returned untouched.  parse() installs this for that one script only, with --pipeline 1 only (the conversion to
+# floats synchronises); without --sampling nothing is installed.
+SAMPLING_SCRIPT = 'test_modelnet_VAE.py'
+SAMPLED = None          # {'k': K, 'n': batches scored, 'sums': [loss, pr, rc]} while --sampling is active
+
+
+def score_sampled_mean(k):
+    global SAMPLED
+    import src.module.nolbo as nolbo
+    SAMPLED = {'k': int(k), 'n': 0, 'sums': np.zeros(3)}
+    base = nolbo._ModelnetBase
+    single = base.getEval
+
+    def getEval(self, inputs, *args, **kw):
+        out = single(self, inputs, *args, **kw)
+        if self._variational:
+            s = self.getSampledEval((inputs[0], inputs[1]), SAMPLED['k'])
+            SAMPLED['sums'] += np.array([float(v) for v in s[1:4]])
+            SAMPLED['n'] += 1
+        return out
+
+    base.getEval = getEval
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -109,6 +149,8 @@ class Progress:
 
     def show(self, epoch, position, total, *groups):
         head = "it:{:04d} rt:{:.2f} Ep_o:{:03d} ".format(self.n, self.elapsed / max(self.n, 1), int(epoch) + 1)
+        if SAMPLED is not None and SAMPLED['n']:
+            groups = groups + (self.group(zip(('sloss', 'spr', 'src'), SAMPLED['sums'] / SAMPLED['n'])),)
         sys.stdout.write(head + self.pos_fmt.format(position, total) + " ".join(groups) + "  \r")
         sys.stdout.flush()
 

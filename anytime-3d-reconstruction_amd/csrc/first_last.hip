@@ -480,6 +480,9 @@ __global__ __launch_bounds__(256, SW_DEPTH == 1 ? 3 : 2) void final_bce_sweep_ke
 // values = 10 KB per plane instead of 100 x 64, and an output pair reads ONE 8-byte granule per (ah, td) instead of three 16-byte quads:
 // LDS written / 2.5, gathered / 6, 38 KB of LDS and <= 128 VGPRs = four workgroups per CU.  Staging, the counted waits and the voxel math
 // are the sweep kernel's, unchanged.
+// final_mean.hip's final_mean_sweep_kernel repeats this kernel's staging offsets, weight-operand layout, mfma_plane, qkey, Q publish and gather
+// (its loop differs: samples chained, no target load, sums in LDS): a change to the swizzle or the operand layout here belongs there too;
+// tests/test_gpu_sampled.py compares the two kernels' outputs (K = 1, and the trained bf16 engine test).
 constexpr int SWW_LDS = SW_NX * SW_XB + 1024 + 80 * 128;
 __global__ __launch_bounds__(256, 4) void final_bce_sweepw_kernel(const __bf16 *__restrict__ x, const float *__restrict__ w,
                                                                  const float *__restrict__ target, float *__restrict__ probs,

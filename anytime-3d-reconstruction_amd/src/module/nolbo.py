@@ -350,6 +350,66 @@ class _ModelnetBase(object):
         z, _, _ = self._encode_latent(self._dev(inputs), _eps)
         return np.array(DeviceArray(z))
 
+    # ---------------------------------------------------------------- sampled-mean reconstruction (an extension)
+    def _posterior_of(self, enc_out):
+        """(mean | logVar) [B,2L] -> (mean, clipped logVar) [B,L] through the class's own latent op (vv_reparam_kl_fwd's outputs;
+        nolbo.py:1417-1420)."""
+        Lz = self._latent_dim
+        if enc_out.dim() != 2 or enc_out.shape[1] != 2 * Lz:
+            raise ValueError('the encoder must emit [B, %d] (mean | logVar), got %s' % (2 * Lz, tuple(enc_out.shape)))
+        zero = torch.zeros(enc_out.shape[0], Lz, dtype=torch.float32, device=self._device)
+        _, _, _, mean, logvar = _E.reparam_kl(enc_out, zero, Lz, self._act_dt, want_stats=True)
+        return mean, logvar
+
+    def _posterior(self, x):
+        """encoder -> (mean, clipped logVar) [B,L]; classes without a posterior (the autoencoder) raise ValueError."""
+        if not self._variational:
+            raise ValueError('%s has no posterior to sample from (an autoencoder): getSampledEval needs a variational class' % type(self).__name__)
+        return self._posterior_of(self._enc_eng.forward(x))
+
+    def getSampledShape(self, mean, logvar, sampling_num=32, target=None, *, _eps=None, max_decode_batch=256):
+        """The "anytime" reconstruction of the reference's nolbo_test.py:169-177 at latent level: `sampling_num` latents
+        mean + sqrt(exp(logvar)) * eps per object, every one decoded, the occupancy probabilities averaged -- the average formed
+        inside the last decoder layer's kernel.  mean / logvar: [B,L], host or device; `_eps` [B,K,L] injects the draw (torch.randn
+        otherwise).  max(1, max_decode_batch // sampling_num) objects go through the decoder per pass, so the activation memory is
+        that of max_decode_batch samples; an object's result does not depend on the pass it lands in.
+        Returns DeviceArray pred_mean [B,D,D,D,1], or (pred_mean, loss_shape, pr, rc) of the AVERAGED prediction when `target`
+        [B,D,D,D,1] is given (means over all B objects, nolbo.py:1498-1501)."""
+        K = int(sampling_num)
+        if K < 1:
+            raise ValueError('sampling_num must be >= 1, got %r' % (sampling_num,))
+        mean, logvar = self._dev(mean), self._dev(logvar)
+        B, Lz = mean.shape
+        if tuple(logvar.shape) != (B, Lz) or Lz != self._dec_eng.L:
+            raise ValueError('mean / logvar must both be [B,%d], got %s and %s' % (self._dec_eng.L, tuple(mean.shape), tuple(logvar.shape)))
+        eps = torch.randn(B, K, Lz, dtype=torch.float32, device=self._device) if _eps is None else self._dev(_eps)
+        if tuple(eps.shape) != (B, K, Lz):
+            raise ValueError('_eps must be [%d,%d,%d], got %s' % (B, K, Lz, tuple(eps.shape)))
+        y = None if target is None else self._dev(target)
+        per = max(1, int(max_decode_batch) // K)
+        preds, stats = [], []
+        for b0 in range(0, B, per):
+            b1 = min(B, b0 + per)
+            _, z_act = _E.sample_latents(mean[b0:b1], logvar[b0:b1], eps[b0:b1], self._act_dt)
+            p, s, _ = self._dec_eng.forward_mean(z_act, K, None if y is None else y[b0:b1], want_metrics=False)   # metrics: over all B, below
+            preds.append(p)
+            stats.append(s)
+        pred = preds[0] if len(preds) == 1 else torch.cat(preds)
+        if y is None:
+            return DeviceArray(pred)
+        m = _E.shape_metrics(stats[0] if len(stats) == 1 else torch.cat(stats))
+        return DeviceArray(pred), DeviceArray(m[0]), DeviceArray(m[1]), DeviceArray(m[2])
+
+    def getSampledEval(self, inputs, sampling_num=32, *, _eps=None):
+        """inputs = (x, y): the encoder runs once per object, `sampling_num` latents are drawn from its posterior (mean and the clipped
+        logVar of this class's latent op) and getSampledShape scores their averaged reconstruction against y
+        -> (pred_mean, loss_shape, pr, rc).  Classes without a posterior (the autoencoder) raise ValueError."""
+        if not self._variational:       # before anything is uploaded
+            return self._posterior(None)
+        x, y = self._dev_pair(inputs[0], inputs[1])
+        mean, logvar = self._posterior(x)
+        return self.getSampledShape(mean, logvar, sampling_num, y, _eps=_eps)
+
     def eval_forward_device(self, x, y, eps=None):
         """Device-resident core of getEval(missing_prob=0) (reference nolbo.py:1463-1501): what bench.py times.
         x, y: float32 CUDA tensors [B,D,D,D,1]; returns (pred, stats [B,4], metrics [4], kl [B] or None), all on device."""
@@ -491,6 +551,9 @@ class nolboSingleObject_VAE(_ModelnetBase):
         eps = torch.randn(enc_out.shape[0], Lz, dtype=torch.float32, device=self._device) if eps is None else self._dev(eps)
         z, z_act, kl, _, _ = _E.reparam_kl(enc_out, eps, Lz, self._act_dt)
         return z, z_act, kl
+
+    def _posterior(self, x):
+        return self._posterior_of(self._dev(self._encoder_2d(x, training=False)).contiguous())
 
     def _encode_decode_seed(self, x, eps=None):
         """No voxel encoder here (the latent comes from the 2D encoder / supplied head outputs): the split calls."""

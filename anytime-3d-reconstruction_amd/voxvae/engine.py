@@ -461,14 +461,9 @@ class DecoderEngine(_EngineBase):
             self.plan.append(_Layer('D%d' % (i + 1), route, L.VV_FP8 if fp8[i - 1] else self.dt, odt,
                                     images.get(R.ROUTE_IMAGE[R.CONVT][route]), images))
 
-    def forward(self, z_act, target=None, want_logits=False, gamma=0.6, epsilon=1e-7, want_metrics=False, h1=None):
-        """z_act: [B,L] in the activation dtype.  target: float32 [B,D,D,D,1] or None.
-        Returns (out, logits, stats): out = probabilities (final_activation 'sigmoid') or logits;
-        stats float32 [B,4] = per-sample (bce, TP, FP, FN) against target (zeros if None).
-        want_metrics: also return float32 [4] = (mean bce, precision, recall, IoU) -- nolbo.py:1498-1501 -- from the same
-        reduction launch as `stats` (a fourth return value).
-        h1: the output of the first (stride-1) decoder layer [B,S,S,S,C0] when the fused latent tail has produced it already
-        (z_act is then not read)."""
+    def _hidden(self, z_act, h1, final_fp8):
+        """The layers in front of the last one (D0 ... D(n-1)), shared by forward and forward_mean -> (h [B,side^3,C], its element type,
+        side, B).  final_fp8: the last hidden layer may be stored as e4m3fn for the fp8 form of the last layer (routes.final_takes_fp8)."""
         self.ensure_packed()
         f, pk, st, S, D = self.filters, self.packed, _stream(), self.S, self.D
         lin = S ** 3 * self.ch
@@ -498,12 +493,24 @@ class DecoderEngine(_EngineBase):
             if ly.idt == L.VV_FP8 and hdt != L.VV_FP8:
                 h = self._as_fp8(h, ly.name + 'c')
             odt = ly.odt
-            if ly.route == 'direct_fp8' and i == len(f) - 2 and R.final_takes_fp8(2 * side, B, self.switches):
+            if final_fp8 and ly.route == 'direct_fp8' and i == len(f) - 2 and R.final_takes_fp8(2 * side, B, self.switches):
                 odt = L.VV_FP8
             o = self._empty(B, 2 * side, 2 * side, 2 * side, f[i], dtype=torch.uint8 if odt == L.VV_FP8 else None)
             R.launch_convT(functools.partial(self._call, ly.name), ly.route, self.ws, h, ly.w, pk['scale%d' % i], pk['shift%d' % i], o,
                            B, side, f[i - 1], f[i], self.act, self.dt, odt, st)
             h, side, hdt = o, 2 * side, odt
+        return h, hdt, side, B
+
+    def forward(self, z_act, target=None, want_logits=False, gamma=0.6, epsilon=1e-7, want_metrics=False, h1=None):
+        """z_act: [B,L] in the activation dtype.  target: float32 [B,D,D,D,1] or None.
+        Returns (out, logits, stats): out = probabilities (final_activation 'sigmoid') or logits;
+        stats float32 [B,4] = per-sample (bce, TP, FP, FN) against target (zeros if None).
+        want_metrics: also return float32 [4] = (mean bce, precision, recall, IoU) -- nolbo.py:1498-1501 -- from the same
+        reduction launch as `stats` (a fourth return value).
+        h1: the output of the first (stride-1) decoder layer [B,S,S,S,C0] when the fused latent tail has produced it already
+        (z_act is then not read)."""
+        f, st, D = self.filters, _stream(), self.D
+        h, hdt, side, B = self._hidden(z_act, h1, True)
         if target is None:
             target = torch.zeros(B, D, D, D, 1, dtype=torch.float32, device=self.device)
         elif target.dtype != torch.float32 or target.numel() != B * D ** 3 or not target.is_contiguous():
@@ -521,6 +528,49 @@ class DecoderEngine(_EngineBase):
         self._call('D%d' % len(f), 'vv_convT3d_final_bce_fwd', L.ptr(h), L.ptr(self.params['convT%d/kernel' % (len(f) - 1)]), L.ptr(target),
                L.ptr(probs), L.ptr(logits), L.ptr(stats), B, side, f[-2], gamma, epsilon, hdt, L.ptr(ws), ws.numel(), st)
         return (probs if self.final_sigmoid else logits), logits, stats
+
+    def forward_mean(self, z_act, samples, target=None, h1=None, gamma=0.6, epsilon=1e-7, want_metrics=True):
+        """Sampled-mean reconstruction (nolbo_test.py:174-177): z_act [B*K,L] holds K = `samples` latents per object, sample k of object b
+        in row b*K + k (sample_latents).  D0 ... D(n-1) run as in forward at batch B*K; the last layer averages the K occupancy
+        probabilities of an object inside the kernel (vv_convT3d_final_mean_fwd) and scores the average.
+        Returns (mean_probs float32 [B,D,D,D,1], stats [B,4] = (bce, TP, FP, FN) of the averaged prediction or None, metrics float32 [4] =
+        (mean bce, precision, recall, IoU) or None); stats and metrics need a target [B,D,D,D,1]; want_metrics=False skips the metrics
+        launch (a caller that scores several passes together)."""
+        if not self.final_sigmoid:
+            raise NotImplementedError("forward_mean averages probabilities: final_activation must be 'sigmoid' (an average of logits is "
+                                      "not the reference's quantity)")
+        K = int(samples)
+        if K < 1:
+            raise ValueError('samples must be >= 1, got %r' % (samples,))
+        f, st, D = self.filters, _stream(), self.D
+        h, hdt, side, BK = self._hidden(z_act, h1, False)       # the last hidden layer in the engine's dtype: the kernel takes bf16 / f32
+        if BK % K:
+            raise ValueError('%d latents do not divide into objects of %d samples' % (BK, K))
+        B = BK // K
+        if target is not None and (target.dtype != torch.float32 or target.numel() != B * D ** 3 or not target.is_contiguous()):
+            raise ValueError('target must be contiguous float32 [B,%d,%d,%d,1]' % (D, D, D))
+        mean_probs = self._empty(B, D, D, D, 1, dtype=torch.float32)
+        stats = self._empty(B, 4, dtype=torch.float32) if target is not None else None
+        ws = self.ws.get(L.load().vv_convT3d_final_mean_workspace_bytes(B, K, side))
+        self._call('D%dm' % len(f), 'vv_convT3d_final_mean_fwd', L.ptr(h), L.ptr(self.params['convT%d/kernel' % (len(f) - 1)]), L.ptr(target),
+                   L.ptr(mean_probs), L.ptr(stats), B, K, side, f[-2], gamma, epsilon, hdt, L.ptr(ws), ws.numel(), st)
+        return mean_probs, stats, (shape_metrics(stats) if (stats is not None and want_metrics) else None)
+
+
+def sample_latents(mean, logvar, eps, act_dtype):
+    """K draws per object (nolbo_test.py:169-173; function.py:35-38): mean / logvar float32 [B,L], eps [B,K,L] ->
+    (z float32 [B*K,L], z_act = the same values in act_dtype), row b*K + k = mean[b] + sqrt(exp(logvar[b])) * eps[b,k]."""
+    B, K, Lz = eps.shape
+    if tuple(mean.shape) != (B, Lz) or tuple(logvar.shape) != (B, Lz):
+        raise ValueError('mean / logvar must be [%d,%d] for eps %s' % (B, Lz, tuple(eps.shape)))
+    for t in (mean, logvar, eps):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('sample_latents takes contiguous float32 tensors')
+    z = torch.empty(B * K, Lz, dtype=torch.float32, device=eps.device)
+    z_act = z if act_dtype == L.VV_F32 else torch.empty(B * K, Lz, dtype=torch.bfloat16, device=eps.device)
+    L.call('vv_sample_latents', L.ptr(mean), L.ptr(logvar), L.ptr(eps), L.ptr(z), L.ptr(z_act) if act_dtype != L.VV_F32 else None,
+           act_dtype, B, K, Lz, _stream())
+    return z, z_act
 
 
 def reparam_kl(enc_out, eps, latent, act_dtype, drop_mask=None, drop_scale=1.0, want_stats=False):

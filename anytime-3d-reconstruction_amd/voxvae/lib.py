@@ -87,6 +87,9 @@ SIGNATURES = {
     'vv_convT3d_final_bce_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _sz, _vp]),
     'vv_convT3d_final_bce_metrics_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _sz, _vp]),
     'vv_shape_metrics': (_i, [_vp, _vp, _i, _vp]),
+    'vv_sample_latents': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'vv_convT3d_final_mean_workspace_bytes': (_sz, [_i, _i, _i]),
+    'vv_convT3d_final_mean_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _sz, _vp]),
     'vv_latent_mask_fill': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     'vv_nearest_category': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     'vv_latent_correct': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -258,6 +258,31 @@ int vv_convT3d_final_bce_metrics_fwd(const void *x, const float *w_keras, const 
 int vv_shape_metrics(const float *stats, float *out4, int batch, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Sampled-mean reconstruction (final_mean.hip): the "anytime" inference of nolbo_test.py:167-180 -- K latents drawn from
+ * an object's posterior, every one decoded, the occupancy PROBABILITIES averaged.
+ * --------------------------------------------------------------------------------------------------------- */
+/* The K draws of nolbo_test.py:169-173 (`sampling(mean, logVar)` K times; function.py:35-38) in one launch:
+ * z[(b K + k), l] = mean[b,l] + sqrt(exp(logvar[b,l])) * eps[b,k,l].  mean/logvar [B,L], eps [B,K,L] (the injected
+ * tf.random.normal draw), z float32 [B K, L] (may be NULL), z_act the same values in act_dtype (VV_F32 / VV_BF16; may be
+ * NULL; both NULL: VV_ERR_NULL).  Nothing is clipped: the caller passes the log-variance its model class uses. */
+int vv_sample_latents(const float *mean, const float *logvar, const float *eps, float *z, void *z_act, int act_dtype,
+                      int objects, int samples, int latent, void *stream);
+/* The last decoder layer over the K samples of each object with `tf.reduce_mean(decoder(latents), axis=0)`
+ * (nolbo_test.py:174-177) inside the kernel: x [B K, side^3, 64] (VV_F32 / VV_BF16; sample k of object b is row b K + k),
+ * w_keras [4,4,4,1,64]; mean_probs [B,(2 side)^3] float32 = (1/K) sum_k sigmoid(logit_k), summed in float32 in a fixed order
+ * (autoencoder3D.py:129-136).  target [B,(2 side)^3] float32 or NULL; stats [B,4] = (bce, TP, FP, FN) of the AVERAGED
+ * prediction (binary_loss with the float32 epsilon clip, counts at mean >= 0.5: function.py:73-82, 100-115), required
+ * exactly when target is given.  1 <= samples <= 1024, objects * samples <= 65535; with VV_BF16 at side >= 8 the samples of ONE
+ * object must also stay below 2 GiB (32-bit buffer offsets: samples * side^3 * 128 B, i.e. samples < 512 at side 32, < 64 at side
+ * 64), else VV_ERR_SHAPE; larger calls are cut into launches of whole objects.  Per-sample probabilities and logits
+ * never reach device memory.  The workspace holds the stats partials and, when the K samples of an object are split over
+ * workgroups to fill the chip, at most 8 float32 partial grids per object; it does not depend on samples for samples >= 8. */
+size_t vv_convT3d_final_mean_workspace_bytes(int objects, int samples, int side);
+int vv_convT3d_final_mean_fwd(const void *x, const float *w_keras, const float *target, float *mean_probs, float *stats,
+                              int objects, int samples, int side, int cin, float gamma, float epsilon, int dtype,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Missing-modality evaluation (nolbo.py:1472-1518; AE: 1277-1322; Pascal: 877-918).  prototypes = the
  * category_vectors array [C,L]; mask [B,L] in {0,1} is the np.random.choice draw of nolbo.py:1475, injected. */
 
