@@ -23,6 +23,8 @@ __global__ void mask_fill_kernel(const float *__restrict__ z, const float *__res
 }
 
 // argmin_c sum_j mask_j * (z_j - P_cj)^2, first minimum (tf.argmin)   -- nolbo.py:1489-1493, 1505-1506
+// Only distances below +inf compete (a NaN or +inf distance never does); a row without one gets index 0, so the index written is
+// always in [0, C) and vv_latent_correct's gather stays inside the prototypes whatever the latent holds.
 __global__ __launch_bounds__(64) void nearest_category_kernel(const float *__restrict__ z, const float *__restrict__ mask,
                                                               const float *__restrict__ protos, int C, int *__restrict__ idx,
                                                               int L) {
@@ -43,7 +45,7 @@ __global__ __launch_bounds__(64) void nearest_category_kernel(const float *__res
         const int oi = __shfl_xor(besti, o, 64);
         if (ob < best || (ob == best && oi < besti)) { best = ob; besti = oi; }
     }
-    if (lane == 0) idx[b] = besti;
+    if (lane == 0) idx[b] = best < INFINITY ? besti : 0;
 }
 
 // z_prior = P[idx] + eps2 (sampling with logVar = 0); z_corr = where(mask == 0, z_prior, z)   -- nolbo.py:1507-1510
@@ -175,6 +177,7 @@ VV_EXPORT int vv_latent_mask_fill(const float *z, const float *mask, const float
                                   void *z_act, int act_dtype, int batch, int latent, void *stream) {
     if (!z || !mask || !prototypes || !z_out) return VV_ERR_NULL;
     if (batch <= 0 || latent <= 0 || classes <= 0) return VV_ERR_SHAPE;
+    if (z_act && act_dtype != VV_F32 && act_dtype != VV_BF16) return VV_ERR_DTYPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((batch * latent + 255) / 256), block(256);
     if (z_act && act_dtype == VV_BF16)
@@ -199,6 +202,7 @@ VV_EXPORT int vv_latent_correct(const float *z, const float *mask, const float *
                                 float *z_corr, void *z_act, int act_dtype, int batch, int latent, void *stream) {
     if (!z || !mask || !prototypes || !argmin || !eps2 || !z_corr) return VV_ERR_NULL;
     if (batch <= 0 || latent <= 0) return VV_ERR_SHAPE;
+    if (z_act && act_dtype != VV_F32 && act_dtype != VV_BF16) return VV_ERR_DTYPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((batch * latent + 255) / 256), block(256);
     if (z_act && act_dtype == VV_BF16)

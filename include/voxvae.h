@@ -286,13 +286,18 @@ int vv_convT3d_final_mean_fwd(const void *x, const float *w_keras, const float *
  * Missing-modality evaluation (nolbo.py:1472-1518; AE: 1277-1322; Pascal: 877-918).  prototypes = the
  * category_vectors array [C,L]; mask [B,L] in {0,1} is the np.random.choice draw of nolbo.py:1475, injected. */
 
-/* z_out = z*mask, then where(z_out == 0, mean_c prototypes, z_out)  (nolbo.py:1477-1482). */
+/* z_out = z*mask, then where(z_out == 0, mean_c prototypes, z_out)  (nolbo.py:1477-1482).  z_act (optional) receives the same
+ * values as act_dtype, VV_F32 or VV_BF16; any other act_dtype with z_act given is VV_ERR_DTYPE. */
 int vv_latent_mask_fill(const float *z, const float *mask, const float *prototypes, int classes, float *z_out,
                         void *z_act, int act_dtype, int batch, int latent, void *stream);
-/* argmin[b] = first argmin_c sum_j mask_bj (z_bj - P_cj)^2; mask NULL = all ones (nolbo.py:1489-1493, 1505-1506). */
+/* argmin[b] = first argmin_c sum_j mask_bj (z_bj - P_cj)^2; mask NULL = all ones (nolbo.py:1489-1493, 1505-1506).
+ * argmin[b] is always in [0, classes): only distances below +inf compete (NaN and +inf never do), and a row that has none
+ * (a non-finite latent, say) gets 0. */
 int vv_nearest_category(const float *z, const float *mask, const float *prototypes, int classes, int *argmin, int batch,
                         int latent, void *stream);
-/* z_corr = where(mask == 0, P[argmin] + eps2, z)  (nolbo.py:1507-1510; eps2 = the second normal draw, injected). */
+/* z_corr = where(mask == 0, P[argmin] + eps2, z)  (nolbo.py:1507-1510; eps2 = the second normal draw, injected).  Every
+ * argmin[b] must be in [0, classes) of `prototypes` (what vv_nearest_category writes).  z_act / act_dtype as in
+ * vv_latent_mask_fill. */
 int vv_latent_correct(const float *z, const float *mask, const float *prototypes, const int *argmin, const float *eps2,
                       float *z_corr, void *z_act, int act_dtype, int batch, int latent, void *stream);
 /* acc[0] = mean_b [argmin_b == argmax_c onehot_bc]  (nolbo.py:1493-1494). */

@@ -193,6 +193,25 @@ def binary_loss(x_pred, x_target, epsilon=1e-7, gamma=0.5, b_range=False):
     return -np.sum(g * yt * np.log(yp) + (dt.type(1.0) - g) * (dt.type(1.0) - yt) * np.log(dt.type(1.0) - yp), axis=-1)
 
 
+def binary_loss_f32clip(x_pred, x_target, epsilon=1e-7, gamma=0.5, b_range=False):
+    """function.py:73-82 as a float32 implementation must see it: the probabilities ARE float32, the clip uses the float32
+    constants (1 - 1e-7 is 0.99999988) and 1 - q is formed in float32 (exact there or not, it is the number whose logarithm is
+    taken; log(1 - q) is ill-conditioned near q -> 1, so a float64 1 - q would be another function).  epsilon and gamma are taken
+    at their float32 values, which is what a float32 entry point receives.  Everything after that is float64.
+    Returns (loss [B], terms [B,V]) with loss = -terms.sum(-1), so a caller can form sum |term| for an error bound."""
+    q = np.ascontiguousarray(x_pred, dtype=np.float32)
+    n = int(np.prod(q.shape[1:]))
+    q = q.reshape(-1, n)
+    t = np.asarray(x_target).reshape(-1, n).astype(np.float64)
+    e32 = np.float32(epsilon)
+    yp = np.clip(q, e32, np.float32(1.0) - e32)
+    om = (np.float32(1.0) - yp).astype(np.float64)
+    b, g = float(b_range), float(np.float32(gamma))
+    yt = -b + (2.0 * b + 1.0) * t
+    terms = g * yt * np.log(yp.astype(np.float64)) + (1.0 - g) * (1.0 - yt) * np.log(om)
+    return -terms.sum(-1), terms
+
+
 def voxel_precision_recall(x_target, x_pred, prob=0.5):
     """function.py:100-115 -> (TP, FP, FN) per sample; threshold is >= on the probability."""
     n = int(np.prod(x_target.shape[1:]))
@@ -217,14 +236,45 @@ def split_mean_logvar(enc_out, L):
     return enc_out[..., :L], np.clip(enc_out[..., L:2 * L], -10.0, 10.0)
 
 
-def _nearest_category_acc(z, cats, onehot, mask=None):
-    """nolbo.py:1489-1494 (mask=None) and :1505-1506 (masked distance)."""
+def latent_mask_fill(z, mask, cats):
+    """nolbo.py:1477-1482: z*mask, then every entry that compares equal to 0 becomes the prototype mean of its column.
+    -0.0 == 0, and a latent that is genuinely 0 under a mask of 1 is replaced too: the reference cannot tell them apart."""
+    z = z * mask
+    return np.where(z == 0, cats.mean(axis=0)[None, :] * np.ones_like(z), z)
+
+
+def nearest_category_distances(z, cats, mask=None):
+    """dist[b,c] = sum_j mask_bj (z_bj - P_cj)^2 -- nolbo.py:1489-1492 (mask=None) and :1505 (masked)."""
     d = np.square(z[:, None, :] - cats[None, :, :])
     if mask is not None:
         d = mask[:, None, :] * d
-    dist = d.sum(-1)
-    idx = np.argmin(dist, axis=-1)
-    return idx, np.mean((idx == np.argmax(onehot, axis=-1)).astype(np.float64))
+    return d.sum(-1)
+
+
+def nearest_category(z, cats, mask=None):
+    """tf.argmin of nearest_category_distances over the classes (nolbo.py:1493, 1506): the FIRST minimum, so the first of two
+    identical prototypes wins and a fully masked row (distance 0 to every class) gets 0.  A NaN distance never competes (it is
+    read as +inf) and a row whose distances are all +inf gets 0: the index is in [0, C) whatever the latent holds."""
+    with np.errstate(invalid='ignore', over='ignore'):
+        dist = nearest_category_distances(z, cats, mask)
+    return np.argmin(np.where(np.isnan(dist), np.inf, dist), axis=-1)
+
+
+def latent_correct(z, mask, cats, idx, eps2):
+    """nolbo.py:1507-1510: the prior sample P[idx] + eps2 (sampling with logVar = 0) wherever mask == 0, z elsewhere."""
+    z_prior = sampling(cats[idx], np.zeros_like(z), eps2)
+    return np.where(mask == 0, z_prior, z)
+
+
+def category_accuracy(idx, onehot):
+    """nolbo.py:1493-1494: mean_b [idx_b == argmax_c onehot_bc]; argmax is the first maximum (0 for an all-zero row)."""
+    return np.mean((np.asarray(idx) == np.argmax(onehot, axis=-1)).astype(np.float64))
+
+
+def _nearest_category_acc(z, cats, onehot, mask=None):
+    """nolbo.py:1489-1494 (mask=None) and :1505-1506 (masked distance)."""
+    idx = nearest_category(z, cats, mask)
+    return idx, category_accuracy(idx, onehot)
 
 
 def _shape_metrics(probs, target, gamma=0.6):
@@ -252,8 +302,7 @@ def vae_get_eval(config, enc_p, dec_p, inputs, category_vectors, eps, missing_pr
         mu, lv, z = enc_out, None, enc_out
     if missing_prob > 0:
         m = mask.astype(dtype)
-        z = z * m                                                        # :1477
-        z = np.where(z == 0, cats.mean(axis=0)[None, :] * np.ones_like(z), z)   # :1481-1482
+        z = latent_mask_fill(z, m, cats)                                 # :1477-1482
     else:
         m = np.ones_like(z)
     _, acc = _nearest_category_acc(z, cats, onehot)
@@ -267,8 +316,7 @@ def vae_get_eval(config, enc_p, dec_p, inputs, category_vectors, eps, missing_pr
         out = (probs, loss_shape, pr, rc, acc, 0, 0, 0, 0, 0)            # :1503
         return (out, det) if details else out
     idx, _ = _nearest_category_acc(z, cats, onehot, mask=m)             # :1505-1506
-    z_prior = sampling(cats[idx], np.zeros_like(z), eps2)                # :1507-1509
-    z_corr = np.where(m == 0, z_prior, z)                                # :1510
+    z_corr = latent_correct(z, m, cats, idx, eps2)                       # :1507-1510
     _, acc_c = _nearest_category_acc(z_corr, cats, onehot)              # :1512-1518
     logits_c, probs_c = decoder3D_forward(config['decoder'], dec_p, z_corr, training, dtype)
     bce_c, tp_c, fp_c, fn_c, loss_c, pr_c, rc_c = _shape_metrics(probs_c, y.astype(dtype))

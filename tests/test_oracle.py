@@ -329,3 +329,77 @@ def test_adam_float32_rounding_and_the_units_it_is_measured_in():
         plain, fixed = adam_units(*out, layer, g, m, v, lr_t)[2], adam_units(*out, layer, g, m, v, lr_t, uncancelled=True)[2]
         print('\n[adam float32 emulation, contract=%d] parameter error on N(0, 0.05) weights: %.1f plain units, %.2f uncancelled' % (contract, plain, fixed))
         assert plain > 8 and fixed <= 4, (contract, plain, fixed)
+
+
+@pytest.mark.parametrize('name', ['vae_d32_l64_b2', 'ae_d32_l64_b2', 'vae_d16_l64_b3', 'vae_d64_l16_b1'])
+def test_latent_ops_reproduce_golden_details(name):
+    """The public latent ops (latent_mask_fill / nearest_category / latent_correct / category_accuracy), applied to the details
+    vae_get_eval stored in the fixtures, give the fixtures' z, argmin_masked, z_corr and accuracies bit for bit: vae_get_eval is
+    written on top of them, and the committed goldens pin that rewrite."""
+    g = np.load(os.path.join(GOLDEN, name + '.npz'))
+    D, L, var, B, C = [int(v) for v in g['meta'][:5]]
+    oh, cats = syn.make_onehot(B, C), syn.make_category_vectors(C, L).astype(np.float64)
+    eps, eps2, mask = syn.make_eps(B, L), syn.make_eps(B, L, seed=8), syn.make_mask(B, L, 0.5).astype(np.float64)
+    enc = g['p5_enc_out']
+    z0 = no.sampling(*no.split_mean_logvar(enc, L), eps) if var else enc
+    z = no.latent_mask_fill(z0, mask, cats)
+    np.testing.assert_array_equal(z, g['p5_z'])
+    idx = no.nearest_category(z, cats, mask)
+    np.testing.assert_array_equal(idx, g['p5_argmin_masked'].astype(np.int64))
+    zc = no.latent_correct(z, mask, cats, idx, eps2)
+    np.testing.assert_array_equal(zc, g['p5_z_corr'])
+    assert no.category_accuracy(no.nearest_category(z, cats), oh) == g['p5_scalars'][3]
+    assert no.category_accuracy(no.nearest_category(zc, cats), oh) == g['p5_scalars'][7]
+    assert no.category_accuracy(no.nearest_category(g['p0_z'], cats), oh) == g['p0_scalars'][3]
+
+
+def test_latent_op_quirks():
+    """Each quirk of the missing-modality algebra, stated once on numbers small enough to read."""
+    P = np.array([[1.0, 2.0, 4.0], [3.0, 2.0, 0.0], [1.0, 2.0, 4.0], [-9.0, 6.0, 4.0]])       # rows 0 and 2 are the same prototype
+    mean = P.mean(0)                                                                          # [-1, 3, 3]
+    # -0.0 and a genuine zero under a mask of 1 are replaced by the prototype mean, exactly like a masked entry
+    z = np.array([[5.0, -0.0, 0.0], [7.0, 8.0, 9.0]])
+    mask = np.array([[1.0, 1.0, 1.0], [0.0, 1.0, -0.0]])
+    np.testing.assert_array_equal(no.latent_mask_fill(z, mask, P), [[5.0, mean[1], mean[2]], [mean[0], 8.0, mean[2]]])
+    # a fully masked row has distance 0 to every class: index 0
+    zz = np.array([[1.1, 2.0, 3.9], [3.0, 2.1, 0.2], [50.0, 60.0, 70.0]])
+    mm = np.array([[1.0, 1.0, 1.0], [1.0, 1.0, 1.0], [0.0, 0.0, 0.0]])
+    assert np.all(no.nearest_category_distances(zz, P, mm)[2] == 0)
+    np.testing.assert_array_equal(no.nearest_category(zz, P, mm), [0, 1, 0])        # row 0: prototypes 0 and 2 tie, the first wins
+    np.testing.assert_array_equal(no.nearest_category(zz[:, ::-1], P[::-1, ::-1]), [1, 2, 1])   # ... also when the pair sits at 1 and 3
+    # a non-finite latent cannot push the index out of [0, C): NaN and +inf distances never compete, a row without any other gets 0
+    bad = np.array([[np.inf, 2.0, 4.0], [np.nan, 2.0, 0.0], [3.0, 2.0, 0.1]])
+    np.testing.assert_array_equal(no.nearest_category(bad, P), [0, 0, 1])
+    np.testing.assert_array_equal(no.nearest_category(bad, P, np.array([[0.0, 1.0, 1.0]] * 3)), [0, 0, 1])    # inf * 0 = NaN
+    Pbad = P.copy()
+    Pbad[1, 0] = np.inf
+    np.testing.assert_array_equal(no.nearest_category(bad, Pbad), [0, 0, 0])        # class 1 is out of the race: the next nearest wins
+    # the corrected latent keeps z where mask != 0 (0.5 and 2.0 are not 0) and takes P[idx] + eps2 where it is 0 or -0.0
+    e2 = np.full((2, 3), 0.25)
+    got = no.latent_correct(z, np.array([[0.5, 0.0, 2.0], [-0.0, 1.0, 1.0]]), P, np.array([3, 1]), e2)
+    np.testing.assert_array_equal(got, [[5.0, 6.25, 0.0], [3.25, 8.0, 9.0]])
+    # argmax of an all-zero one-hot row is 0, of a row with two maxima the first
+    oh = np.array([[0.0, 0.0, 0.0], [0.0, 1.0, 1.0], [0.0, 0.0, 1.0], [1.0, 0.0, 0.0]])
+    assert no.category_accuracy([0, 1, 1, 2], oh) == 0.5
+
+
+def test_binary_loss_f32clip_reference():
+    """The loss reference for float32 kernels: float32 clip and float32 1 - q, float64 from there on.  On probabilities away from
+    saturation it is binary_loss in float64 to rounding; at saturation it follows the float32 constants; the terms sum to the loss."""
+    rng = np.random.default_rng(4)
+    p = rng.uniform(0.05, 0.95, (3, 50)).astype(np.float32)
+    y = (rng.random((3, 50)) < 0.4).astype(np.float32)
+    for gamma, br in ((0.5, False), (0.6, False), (1.0, True)):
+        loss, terms = no.binary_loss_f32clip(p, y, gamma=gamma, b_range=br)
+        assert terms.shape == (3, 50) and terms.dtype == np.float64
+        np.testing.assert_array_equal(loss, -terms.sum(-1))
+        np.testing.assert_allclose(loss, no.binary_loss(p.astype(np.float64), y, gamma=gamma, b_range=br), rtol=2e-6)
+    edge = np.array([[0.0, 1.0, 1e-8, np.float32(1 - 1e-7), 0.5]], np.float32)
+    hi = float(np.float32(1.0) - np.float32(1e-7))
+    lo = float(np.float32(1e-7))
+    loss, terms = no.binary_loss_f32clip(edge, np.array([[1.0, 1.0, 0.0, 0.0, 1.0]]), gamma=1.0)
+    np.testing.assert_array_equal(terms[0], [np.log(lo), np.log(hi), 0.0, 0.0, np.log(0.5)])
+    loss, terms = no.binary_loss_f32clip(edge, np.array([[0.0, 0.0, 0.0, 0.0, 0.0]]), gamma=0.0)
+    one_minus_hi = float(np.float32(1.0) - np.float32(hi))                           # 1.1920929e-07, not 1e-7
+    np.testing.assert_array_equal(terms[0], [np.log(float(np.float32(1.0) - np.float32(lo))), np.log(one_minus_hi), np.log(float(np.float32(1.0) - np.float32(1e-7))),
+                                             np.log(one_minus_hi), np.log(0.5)])
