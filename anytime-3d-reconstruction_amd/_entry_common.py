@@ -31,7 +31,9 @@ def make_config(latent_dim=64, voxel=64, variational=True):
     }
 
 
-def parse(description, train=False):
+def parse(description, train=False, extra=None):
+    """extra(ap): a script's own options.  A script that defines them reads --sampling itself (test_modelnet_PR.py: the curve of the
+    sampled-mean reconstruction) and nothing is installed for it below."""
     ap = argparse.ArgumentParser(description=description)
     ap.add_argument('--dataset-path', default=None, help="ModelNet shard directory; default: seeded synthetic voxels")
     ap.add_argument('--voxel', type=int, default=32, help='voxel side (the reference ships 64; BASELINE.json asks for 32)')
@@ -49,9 +51,11 @@ def parse(description, train=False):
     ap.add_argument('--packed-data', action='store_true', help='host loader that keeps the split as bits and serves PackedVoxels batches (1 bit per voxel over PCIe)')
     ap.add_argument('--pipeline', type=int, default=1, help='test_modelnet_VAE.py: batches in flight (voxvae.streams.HostPipeline); 1 = the reference\'s synchronous loop')
     ap.add_argument('--dump-dir', default=None, help='test_modelnet_VAE.py: save <missing_pr>_cl_label/_gt/_pred.npy here (reference :159-165)')
-    ap.add_argument('--sampling', type=int, default=0, help='test_modelnet_VAE.py only: also score the sampled-mean reconstruction over this many latents per object (0 = off); needs --pipeline 1')
+    ap.add_argument('--sampling', type=int, default=0, help='test_modelnet_VAE.py: also score the sampled-mean reconstruction over this many latents per object (0 = off); needs --pipeline 1.  test_modelnet_PR.py: also accumulate that reconstruction\'s curve')
+    if extra is not None:
+        extra(ap)
     a = ap.parse_args()
-    if a.sampling:
+    if a.sampling and extra is None:
         # one script owns the option: elsewhere (train + test getEval in one loop, other model classes) its numbers would mean something else
         if os.path.basename(sys.argv[0]) != SAMPLING_SCRIPT:
             ap.error('--sampling is an option of %s' % SAMPLING_SCRIPT)

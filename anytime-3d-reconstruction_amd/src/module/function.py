@@ -71,3 +71,17 @@ def voxelPrecisionRecall(xTarget, xPred, prob=0.5):
     tp, fp, fn = (torch.empty(B, dtype=torch.float32, device=p.device) for _ in range(3))
     _L.call('vv_voxel_precision_recall', _L.ptr(t), _L.ptr(p), float(prob), _L.ptr(tp), _L.ptr(fp), _L.ptr(fn), B, V, _st())
     return DeviceArray(tp), DeviceArray(fp), DeviceArray(fn)
+
+
+def voxelPrecisionRecallCurve(xTarget, xPred, probs, inclusive=True):
+    """voxelPrecisionRecall at every threshold of `probs` in one pass over the data (vv_pr_curve_accumulate; the sweep the reference's
+    notebooks run on the host, modelnetAE3.ipynb cell 2) -> (TP, FP, FN), each [B, T] float32 like its single-threshold sibling.
+    inclusive=True counts p >= prob as function.py:110 does; False counts p > prob (the notebook's compare); one bool or one per
+    threshold."""
+    from voxvae.prcurve import PRCurve
+    p = _dev(xPred)
+    B = p.shape[0]
+    curve = PRCurve(np.atleast_1d(np.asarray(probs, dtype=np.float64)), inclusive, groups=B, device=p.device)
+    curve.update(xTarget, p, group=torch.arange(B, dtype=torch.int32, device=p.device))
+    tp, fp, fn, _, _ = curve.counts_device()
+    return DeviceArray(tp.float()), DeviceArray(fp.float()), DeviceArray(fn.float())

@@ -410,6 +410,30 @@ class _ModelnetBase(object):
         mean, logvar = self._posterior(x)
         return self.getSampledShape(mean, logvar, sampling_num, y, _eps=_eps)
 
+    # ---------------------------------------------------------------- precision / recall curves (an extension)
+    def getPRCurve(self, inputs, curve, category_vectors=None, missing_prob=0.0, sampling_num=0, corrected=None, *, group=None,
+                   training=False, _eps=None, _mask=None, _eps2=None):
+        """getEval (or, with sampling_num > 0, getSampledEval over that many latents per object) followed by one more launch that
+        adds this batch's (target, prediction) to `curve`, a voxvae.prcurve.PRCurve -- the threshold sweep the reference runs on the
+        host over the saved `_gt.npy` / `_pred.npy` (modelnetAE3.ipynb cell 2) without the probabilities leaving the device.  With
+        missing_prob > 0 the corrected prediction is added to `corrected`, a second PRCurve, when one is given.  group: the curves'
+        per-sample group (int [B] or one-hot [B, G], e.g. the batch's class list for per-category curves).  The target is uploaded
+        once and shared with the evaluation.  Returns what the underlying call returns; nothing here synchronises."""
+        y = self._dev(inputs[1])
+        inputs = ((y if inputs[0] is inputs[1] else inputs[0]), y) + tuple(inputs[2:])
+        if sampling_num > 0:
+            if missing_prob or training or _mask is not None or _eps2 is not None:
+                raise ValueError('the sampled-mean reconstruction takes neither missing_prob nor training / _mask / _eps2')
+            out = self.getSampledEval((inputs[0], y), sampling_num, _eps=_eps)
+        else:
+            # positional: the second argument is `category_indices` in the class with a learned prior
+            out = self.getEval(inputs, *(() if category_vectors is None else (category_vectors,)), training=training,
+                               missing_prob=missing_prob, _eps=_eps, _mask=_mask, _eps2=_eps2)
+        curve.update(y, out[0], group=group)
+        if corrected is not None and missing_prob > 0 and len(out) == 10:
+            corrected.update(y, out[5], group=group)
+        return out
+
     def eval_forward_device(self, x, y, eps=None):
         """Device-resident core of getEval(missing_prob=0) (reference nolbo.py:1463-1501): what bench.py times.
         x, y: float32 CUDA tensors [B,D,D,D,1]; returns (pred, stats [B,4], metrics [4], kl [B] or None), all on device."""

@@ -325,6 +325,29 @@ int vv_regulizer_loss(const float *mean, const float *logvar, const float *class
 int vv_sampling(const float *mu, const float *logvar, const float *eps, float *out, long n, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Precision / recall-vs-threshold counts (pr_curve.hip): the sweep of modelnetAE3.ipynb / pascalAE3.ipynb cell 2 over the
+ * `_gt.npy` / `_pred.npy` arrays of test_modelnet_VAE.py:128-130, 159-165, in one streaming pass over device memory for every threshold.
+ *   pred        float32 [batch][voxels] probabilities
+ *   target      float32 [batch][voxels] (target_packed == 0; a voxel is occupied iff y > 0.5) or packed bits (target_packed == 1: voxel v is
+ *               bit v & 7 of byte v >> 3 of a row of voxels / 8 bytes, the layout of vv_pack_bits; voxels % 8 != 0: VV_ERR_SHAPE)
+ *   thresholds  float32 [nthr], 1 <= nthr <= 256, any order, duplicates allowed.  For threshold i
+ *               TP_i = #{occupied and p > t_i}, FP_i = #{not occupied and p > t_i} with an ordered float32 `>`: a NaN probability exceeds
+ *               nothing (it still counts in `totals`), denormals compare as they do in IEEE arithmetic (nothing is flushed).  FN_i is not
+ *               stored: FN_i = occupied - TP_i.  An inclusive threshold is a host matter: p >= t <=> p > nextafter(t, -inf) in float32.
+ *   sorted      != 0: the caller's promise that thresholds are non-decreasing (a wave then stops at the first threshold none of its
+ *               voxels exceeds).  A false promise may give wrong counts, never a wrong address.
+ *   group       int32 [batch] or NULL (everything in group 0): sample b is counted into group[b]; a sample whose index is outside
+ *               [0, ngroups) is counted nowhere and writes nowhere.
+ *   tp_fp       int64 [ngroups][nthr][2] = (TP, FP), ADDED to;  totals int64 [ngroups][2] = (occupied voxels, all voxels), ADDED to:
+ *               one pair of buffers accumulates a whole test split.  All arithmetic is integer (32-bit partial counts per 4096-voxel
+ *               piece of a sample in the workspace, added to the accumulators by a second launch): the result does not depend on any order.
+ * Rows need no alignment beyond that of their element type. */
+size_t vv_pr_curve_workspace_bytes(int batch, long voxels, int nthr);
+int vv_pr_curve_accumulate(const float *pred, const void *target, int target_packed, const float *thresholds, int nthr, int sorted,
+                           const int *group, int ngroups, long long *tp_fp, long long *totals, void *workspace, size_t workspace_bytes,
+                           int batch, long voxels, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Training path (nolboSingleObject_modelnet_category_{VAE,AE}.fit, nolbo.py:1411-1447 / 1230-1258).  float32.
  * Data gradients reuse the forward kernels: d(Conv3D k4 s2)/d(input) = vv_convT3d_k4s2_fwd with the SAME Keras
  * kernel array packed by vv_pack_convT_k4s2 (read as [4,4,4,Cout_T = Cin, Cin_T = Cout]); d(Conv3DTranspose k4 s2)/
