@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+
+#include <type_traits>
 
 #include "../../include/voxvae.h"
 
@@ -48,7 +51,6 @@ static inline int vv_log2(int v) {
 }
 // Buffer descriptors carry 32-bit offsets: a launch covers at most 2 GiB of its largest per-sample-indexed tensor; larger batches
 // go out as several launches over sample ranges (samples are independent).  VV_CHUNK_SAMPLES caps the range (tests).
-#include <stdlib.h>
 // Test hooks (kernel-form overrides for A/B tests and microbenchmarks) exist only in the build with -DVV_TEST_HOOKS
 // (lib/libvoxvae_hooks.so, loaded by tests that set one of the VV_* variables); the release library reads no environment
 // variable at all: vv_hook("...") is a null pointer there and the name does not reach the binary.
@@ -57,6 +59,9 @@ static inline const char *vv_hook(const char *name) { return getenv(name); }
 #else
 #define vv_hook(name) (static_cast<const char *>(nullptr))
 #endif
+// A hook that carries a number: vv_hook_int(vv_hook(name), default).  The name stays inside vv_hook, which drops it in the release
+// build (and tests/test_abi.py finds every hook the sources read by that spelling); there this folds to the default.
+static inline long vv_hook_int(const char *e, long dflt) { return e ? atol(e) : dflt; }
 static inline int vv_chunk_samples(size_t sample_bytes, int batch) {
     size_t per = sample_bytes ? 0x7FFFFFFFull / sample_bytes : (size_t)batch;
     if (const char *e = vv_hook("VV_CHUNK_SAMPLES")) {
@@ -81,6 +86,48 @@ static inline int vv_launch_status() {
     if (e == hipSuccess) return VV_OK;
     vv_tls_last_hip_error = (int)e;
     return VV_ERR_LAUNCH;
+}
+
+// Dynamic LDS above 64 KiB needs an opt-in per kernel: once per process and kernel instantiation (the static local is keyed on
+// the kernel pointer).  vv_allow_lds<&kernel>(bytes) goes in front of the launch.
+template <auto Kernel>
+static inline void vv_allow_lds(int bytes) {
+    static const bool once = [bytes] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        return true;
+    }();
+    (void)once;
+}
+
+// 1-D grid of 256-thread blocks over n items for the grid-stride kernels.
+static inline int vv_grid_1d(long n, int cap = 8192) {
+    const long g = (n + 255) / 256;
+    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
+// The counted wait of the LDS-DMA / asm-load rings: vector-memory operations retire in order, so vmcnt(N) = "all but the N youngest".
+template <int N>
+__device__ __forceinline__ void vv_wait_vm() {
+    asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory");
+}
+
+// The run-time activation code as a compile-time constant: fn(std::integral_constant<int, VV_ACT_*>{}, further arguments...); an
+// unknown code is VV_ACT_NONE.  This is the one such switch.  Kernels use the macro, so that the four arms are calls in the kernel's
+// own body as if written there: behind a function the inliner, working bottom-up, first merges the four epilogues inside the wrapper
+// and simplifies them there, and the kernels with large epilogues (convT_direct*, sd_kernel, pg_kernel) come out as different code.
+// Host launchers, which pick a kernel instantiation, use the function.
+#define VV_WITH_ACT(act, fn, ...)                                                                      \
+    do {                                                                                               \
+        switch (act) {                                                                                 \
+            case VV_ACT_ELU: fn(std::integral_constant<int, VV_ACT_ELU>{}, ##__VA_ARGS__); break;      \
+            case VV_ACT_RELU: fn(std::integral_constant<int, VV_ACT_RELU>{}, ##__VA_ARGS__); break;    \
+            case VV_ACT_LRELU: fn(std::integral_constant<int, VV_ACT_LRELU>{}, ##__VA_ARGS__); break;  \
+            default: fn(std::integral_constant<int, VV_ACT_NONE>{}, ##__VA_ARGS__); break;             \
+        }                                                                                              \
+    } while (0)
+template <typename Fn>
+static inline void vv_with_act(int act, Fn &&fn) {
+    VV_WITH_ACT(act, fn);
 }
 
 // autoencoder3D.py:33-38: ELU(alpha 1) / ReLU / LeakyReLU(alpha 0.3, the Keras default)

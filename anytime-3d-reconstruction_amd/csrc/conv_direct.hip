@@ -18,18 +18,9 @@
 //                chunk c+1 then fly under the last 4 MFMAs of chunk c; fragment reads are inline asm, one k-step ahead
 //   epilogue   : folded BN + activation, LDS transpose, 16-byte stores of whole channel rows (the 256 outputs of a
 //                workgroup are contiguous in y when the output side is 8)
-#include <stdlib.h>
-
-#include <type_traits>
-
-#include "common.h"
+#include "direct_common.h"
 
 namespace {
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory");
-}
 
 constexpr int CD_CIN = 64, CD_COUT = 128;
 constexpr int CD_RB = CD_CIN * 2;                 // bytes per voxel row
@@ -52,14 +43,8 @@ __global__ __launch_bounds__(512, 1) void conv_direct_kernel(const __bf16 *__res
     const int wm = wave >> 1, wn = wave & 1;
     const int lo = dout_log2, no = 1 << lo, li = lo + 1, n = 1 << li;
 
-    // XCD-aware order: consecutive boxes (same sample) run on one XCD and share its L2
-    const int nwg = gridDim.x;
-    int blk = (nwg & 7) == 0 ? (int)(blockIdx.x & 7) * (nwg >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    const int bxw = no >> 3, bxh = no >> 3, bxd = no >> 2;
-    const int bw = blk % bxw; blk /= bxw;
-    const int bh = blk % bxh; blk /= bxh;
-    const int bd = blk % bxd; const int b = blk / bxd;
-    const int od0 = bd * 4, oh0 = bh * 8, ow0 = bw * 8;
+    const VvDirectBox box = vv_direct_box(no);
+    const int b = box.b, od0 = box.od0, oh0 = box.oh0, ow0 = box.ow0;
 
     const u32x4 rsx = vv_make_rsrc(x, x_bytes), rsw = vv_make_rsrc(w, w_bytes);
     const unsigned lds0 = (unsigned)(unsigned long long)(lptr_t)smem;
@@ -96,7 +81,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct_kernel(const __bf16 *__res
     issue_w(0);
     issue_w(1);
     issue_w(2);
-    wait_vm<0>();
+    vv_wait_vm<0>();
     __syncthreads();
 
     // ---- consumer addressing (LDS byte addresses)
@@ -160,7 +145,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct_kernel(const __bf16 *__res
             CD_WAITFRAG(Q, 0);                     // every LDS read of chunk c has returned: its stage may be refilled
             // chunk c+1's weights (and, before tap 0 of the next phase, the whole next tile) have landed.  Pieces issued
             // after w(c+1): [x piece of tap A-1] w(c+2) x2; tap 7 needs the x piece of tap 6, which precedes w(c+2).
-            wait_vm<(A == 0 || A == 7) ? 2 : 3>();
+            vv_wait_vm<(A == 0 || A == 7) ? 2 : 3>();
             __syncthreads();
             if (A < 7) issue_x(q + 1, A);
             issue_w(c + 3);
@@ -177,7 +162,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct_kernel(const __bf16 *__res
         tap(std::integral_constant<int, 7>{});
     }
     CD_WAITFRAG(P, 0);                              // the look-ahead reads of the non-existent chunk 64
-    wait_vm<0>();                                   // trailing zero-fill pieces still target LDS
+    vv_wait_vm<0>();                                // trailing zero-fill pieces still target LDS
     __syncthreads();
 
     // ---- epilogue: lane = output (wm, mt, fr); registers walk channels
@@ -200,57 +185,14 @@ __global__ __launch_bounds__(512, 1) void conv_direct_kernel(const __bf16 *__res
 #pragma unroll
             for (int g = 0; g < 4; ++g) shv[nt][g] = *reinterpret_cast<const f32x4 *>(shift + wn * 64 + nt * 32 + 8 * g + 4 * fh);
     }
-    auto fill = [&](auto act_c, auto fp8_c) {
-        constexpr int ACT = decltype(act_c)::value;
-        constexpr bool FP8 = decltype(fp8_c)::value;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int c = wn * 64 + nt * 32 + 8 * g + 4 * fh;
-                    const f32x4 sc = scv[nt][g], sh = shv[nt][g];
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float t = acc[nt][mt][4 * g + e] * sc[e] + sh[e];
-                        if (ACT == VV_ACT_ELU) { const float em = __expf(fminf(t, 0.f)) - 1.f; t = t > 0.f ? t : em; }
-                        else if (ACT == VV_ACT_RELU) t = fmaxf(t, 0.f);
-                        else if (ACT == VV_ACT_LRELU) t = t > 0.f ? t : 0.3f * t;
-                        v[e] = t;
-                    }
-                    char *dst = stage + (wm * 64 + mt * 32 + fr) * CD_SP;
-                    if (FP8) {
-                        *reinterpret_cast<unsigned *>(dst + c) = vv_pack_fp8x4(v);
-                    } else {
-                        bf16x4 o;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] = static_cast<__bf16>(v[e]);
-                        *reinterpret_cast<bf16x4 *>(dst + c * 2) = o;
-                    }
-                }
-    };
+    auto fill = VV_DIRECT_FILL32(CD_SP, wn * 64);
     auto with_out = [&](auto act_c) {
         if (out_fp8) fill(act_c, std::true_type{});
         else fill(act_c, std::false_type{});
     };
-    switch (act) {
-        case VV_ACT_ELU: with_out(std::integral_constant<int, VV_ACT_ELU>{}); break;
-        case VV_ACT_RELU: with_out(std::integral_constant<int, VV_ACT_RELU>{}); break;
-        case VV_ACT_LRELU: with_out(std::integral_constant<int, VV_ACT_LRELU>{}); break;
-        default: with_out(std::integral_constant<int, VV_ACT_NONE>{}); break;
-    }
+    VV_WITH_ACT(act, with_out);
     __syncthreads();
-    const int es = out_fp8 ? 1 : 2;                   // the fp8 form hands the layer's output to an fp8 consumer (e4m3fn)
-    const int cpr = CD_COUT * es / 16;                // 16-byte chunks per output row
-    for (int id = tid; id < 256 * cpr; id += 512) {
-        const int r = id / cpr, cc = id % cpr;
-        const int od = od0 + (r >> 6), oh = oh0 + ((r >> 3) & 7), ow = ow0 + (r & 7);
-        const size_t vox = ((((((size_t)b << lo) + od) << lo) + oh) << lo) + ow;
-        *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(y) + vox * (CD_COUT * es) + cc * 16) =
-            *reinterpret_cast<const uint4 *>(stage + r * CD_SP + cc * 16);
-    }
+    vv_direct_store_box<512, CD_SP, CD_COUT, CD_COUT>(stage, y, box, lo, tid, out_fp8);
 }
 
 __global__ __launch_bounds__(512, 1) void conv_direct16_kernel(const __bf16 *__restrict__ x, const __bf16 *__restrict__ w,
@@ -263,14 +205,8 @@ __global__ __launch_bounds__(512, 1) void conv_direct16_kernel(const __bf16 *__r
     const int wm = wave >> 1, wn = wave & 1;
     const int lo = dout_log2, no = 1 << lo, li = lo + 1, n = 1 << li;
 
-    // XCD-aware order: consecutive boxes (same sample) run on one XCD and share its L2
-    const int nwg = gridDim.x;
-    int blk = (nwg & 7) == 0 ? (int)(blockIdx.x & 7) * (nwg >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    const int bxw = no >> 3, bxh = no >> 3, bxd = no >> 2;
-    const int bw = blk % bxw; blk /= bxw;
-    const int bh = blk % bxh; blk /= bxh;
-    const int bd = blk % bxd; const int b = blk / bxd;
-    const int od0 = bd * 4, oh0 = bh * 8, ow0 = bw * 8;
+    const VvDirectBox box = vv_direct_box(no);
+    const int b = box.b, od0 = box.od0, oh0 = box.oh0, ow0 = box.ow0;
 
     const u32x4 rsx = vv_make_rsrc(x, x_bytes), rsw = vv_make_rsrc(w, w_bytes);
     const unsigned lds0 = (unsigned)(unsigned long long)(lptr_t)smem;
@@ -307,7 +243,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct16_kernel(const __bf16 *__r
     issue_w(0);
     issue_w(1);
     issue_w(2);
-    wait_vm<0>();
+    vv_wait_vm<0>();
     __syncthreads();
 
     // ---- consumer addressing (LDS byte addresses).  lane = (r, kq): row r of a 16-row fragment, k quarter kq of a 32-deep
@@ -377,7 +313,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct16_kernel(const __bf16 *__r
             CD16_WAIT(Q, 0);                       // every LDS read of chunk c has returned: its stage may be refilled
             // chunk c+1's weights (and, before tap 0 of the next phase, the whole next tile) have landed.  Pieces issued
             // after w(c+1): [x piece of tap A-1] w(c+2) x2; tap 7 needs the x piece of tap 6, which precedes w(c+2).
-            wait_vm<(A == 0 || A == 7) ? 2 : 3>();
+            vv_wait_vm<(A == 0 || A == 7) ? 2 : 3>();
             __syncthreads();
             CD16_SB;
             CD16_MF(Q, 0, 0); CD16_MF(Q, 0, 1);
@@ -403,7 +339,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct16_kernel(const __bf16 *__r
         tap(std::integral_constant<int, 7>{});
     }
     CD16_WAIT(P, 0);                                // the look-ahead reads of the non-existent chunk 64
-    wait_vm<0>();                                   // trailing zero-fill pieces still target LDS
+    vv_wait_vm<0>();                                // trailing zero-fill pieces still target LDS
     __syncthreads();
 
     // ---- epilogue: lane = output (wm, mt, fr); registers walk channels
@@ -420,47 +356,14 @@ __global__ __launch_bounds__(512, 1) void conv_direct16_kernel(const __bf16 *__r
 #pragma unroll
         for (int cot = 0; cot < 4; ++cot) shv[cot] = *reinterpret_cast<const f32x4 *>(shift + wn * 64 + cot * 16 + 4 * kq);
     }
-    auto fill = [&](auto act_c, auto fp8_c) {
-        constexpr int ACT = decltype(act_c)::value;
-        constexpr bool FP8 = decltype(fp8_c)::value;
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-            for (int cot = 0; cot < 4; ++cot) {
-                const int c = wn * 64 + cot * 16 + 4 * kq;
-                const f32x4 sc = scv[cot], sh = shv[cot];
-                const f32x4 v = vv_bn_act4<ACT>(acc[cot][ct], sc, sh);
-                char *dst = stage + (wm * 64 + ct * 16 + r) * CD_SP;
-                if (FP8) {
-                    *reinterpret_cast<unsigned *>(dst + c) = vv_pack_fp8x4(v);
-                } else {
-                    bf16x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = static_cast<__bf16>(v[e]);
-                    *reinterpret_cast<bf16x4 *>(dst + c * 2) = o;
-                }
-            }
-    };
+    auto fill = VV_DIRECT_FILL16(CD_SP, wn * 64);
     auto with_out = [&](auto act_c) {
         if (out_fp8) fill(act_c, std::true_type{});
         else fill(act_c, std::false_type{});
     };
-    switch (act) {
-        case VV_ACT_ELU: with_out(std::integral_constant<int, VV_ACT_ELU>{}); break;
-        case VV_ACT_RELU: with_out(std::integral_constant<int, VV_ACT_RELU>{}); break;
-        case VV_ACT_LRELU: with_out(std::integral_constant<int, VV_ACT_LRELU>{}); break;
-        default: with_out(std::integral_constant<int, VV_ACT_NONE>{}); break;
-    }
+    VV_WITH_ACT(act, with_out);
     __syncthreads();
-    const int es = out_fp8 ? 1 : 2;                   // the fp8 form hands the layer's output to an fp8 consumer (e4m3fn)
-    const int cpr = CD_COUT * es / 16;                // 16-byte chunks per output row
-    for (int id = tid; id < 256 * cpr; id += 512) {
-        const int r = id / cpr, cc = id % cpr;
-        const int od = od0 + (r >> 6), oh = oh0 + ((r >> 3) & 7), ow = ow0 + (r & 7);
-        const size_t vox = ((((((size_t)b << lo) + od) << lo) + oh) << lo) + ow;
-        *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(y) + vox * (CD_COUT * es) + cc * 16) =
-            *reinterpret_cast<const uint4 *>(stage + r * CD_SP + cc * 16);
-    }
+    vv_direct_store_box<512, CD_SP, CD_COUT, CD_COUT>(stage, y, box, lo, tid, out_fp8);
 }
 
 
@@ -490,15 +393,8 @@ __global__ __launch_bounds__(256, 2) void conv_direct16h_kernel(const __bf16 *__
     const int wm = wave;
     const int lo = dout_log2, no = 1 << lo, li = lo + 1, n = 1 << li;
 
-    // XCD-aware order: the two channel halves of a box, then the boxes of a sample, run on one XCD (they read the same tiles)
-    const int nwg = gridDim.x;
-    int blk = (nwg & 7) == 0 ? (int)(blockIdx.x & 7) * (nwg >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    const int nh = blk & 1; blk >>= 1;
-    const int bxw = no >> 3, bxh = no >> 3, bxd = no >> 2;
-    const int bw = blk % bxw; blk /= bxw;
-    const int bh = blk % bxh; blk /= bxh;
-    const int bd = blk % bxd; const int b = blk / bxd;
-    const int od0 = bd * 4, oh0 = bh * 8, ow0 = bw * 8;
+    const VvDirectBox box = vv_direct_box<true>(no);
+    const int b = box.b, od0 = box.od0, oh0 = box.oh0, ow0 = box.ow0, nh = box.nh;
 
     const u32x4 rsx = vv_make_rsrc(x, x_bytes), rsw = vv_make_rsrc(w, w_bytes);
     const unsigned lds0 = (unsigned)(unsigned long long)(lptr_t)smem;
@@ -543,7 +439,7 @@ __global__ __launch_bounds__(256, 2) void conv_direct16h_kernel(const __bf16 *__
     issue_w(0);
     issue_w(1);
     issue_w(2);
-    wait_vm<0>();
+    vv_wait_vm<0>();
     __syncthreads();
 
     // ---- consumer addressing: conv_direct16_kernel's, channel tile base 0 (the workgroup's half starts at stage row 0)
@@ -568,7 +464,7 @@ __global__ __launch_bounds__(256, 2) void conv_direct16h_kernel(const __bf16 *__
     for (int q = 0; q < 8; ++q) {
         if (q > 0) {
             // the refill of THE tile was issued behind the last barrier of phase q - 1 (tap 7 below); it has landed:
-            wait_vm<0>();                           // (also drains the weight pieces issued before them: in-order counter)
+            vv_wait_vm<0>();                        // (also drains the weight pieces issued before them: in-order counter)
             __syncthreads();
         }
         CD16_LD(P, xo[0][0], 0, wo[0] + ((q * 8) % CD_NST) * CDH_WST);      // chunk 8 q, k-step 0
@@ -590,7 +486,7 @@ __global__ __launch_bounds__(256, 2) void conv_direct16h_kernel(const __bf16 *__
             CD16_SB;
             CD16_WAIT(Q, 0);                       // every LDS read of chunk c has returned: its stage may be refilled
             // chunk c+1's weights have landed: the only pieces issued after w(c+1) are the two of w(c+2)
-            wait_vm<2>();
+            vv_wait_vm<2>();
             __syncthreads();
             CD16_SB;
             CD16_MF(Q, 0, 0); CD16_MF(Q, 0, 1);
@@ -630,7 +526,7 @@ __global__ __launch_bounds__(256, 2) void conv_direct16h_kernel(const __bf16 *__
         tap(std::integral_constant<int, 6>{});
         tap(std::integral_constant<int, 7>{});
     }
-    wait_vm<0>();                                   // trailing zero-fill pieces still target LDS
+    vv_wait_vm<0>();                                // trailing zero-fill pieces still target LDS
     __syncthreads();
 
     // ---- epilogue: lane = output (wm, ct, r); registers walk channels nh*64 + 16 cot + 4 kq ..
@@ -646,46 +542,14 @@ __global__ __launch_bounds__(256, 2) void conv_direct16h_kernel(const __bf16 *__
 #pragma unroll
         for (int cot = 0; cot < 4; ++cot) shv[cot] = *reinterpret_cast<const f32x4 *>(shift + nh * CDH_COUT + cot * 16 + 4 * kq);
     }
-    auto fill = [&](auto act_c, auto fp8_c) {
-        constexpr int ACT = decltype(act_c)::value;
-        constexpr bool FP8 = decltype(fp8_c)::value;
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-            for (int cot = 0; cot < 4; ++cot) {
-                const int c = cot * 16 + 4 * kq;
-                const f32x4 v = vv_bn_act4<ACT>(acc[cot][ct], scv[cot], shv[cot]);
-                char *dst = stage + (wm * 64 + ct * 16 + r) * CDH_SP;
-                if (FP8) {
-                    *reinterpret_cast<unsigned *>(dst + c) = vv_pack_fp8x4(v);
-                } else {
-                    bf16x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = static_cast<__bf16>(v[e]);
-                    *reinterpret_cast<bf16x4 *>(dst + c * 2) = o;
-                }
-            }
-    };
+    auto fill = VV_DIRECT_FILL16(CDH_SP, 0);
     auto with_out = [&](auto act_c) {
         if (out_fp8) fill(act_c, std::true_type{});
         else fill(act_c, std::false_type{});
     };
-    switch (act) {
-        case VV_ACT_ELU: with_out(std::integral_constant<int, VV_ACT_ELU>{}); break;
-        case VV_ACT_RELU: with_out(std::integral_constant<int, VV_ACT_RELU>{}); break;
-        case VV_ACT_LRELU: with_out(std::integral_constant<int, VV_ACT_LRELU>{}); break;
-        default: with_out(std::integral_constant<int, VV_ACT_NONE>{}); break;
-    }
+    VV_WITH_ACT(act, with_out);
     __syncthreads();
-    const int es = out_fp8 ? 1 : 2;
-    const int cpr = CDH_COUT * es / 16;               // 16-byte chunks of this workgroup's half of an output row
-    for (int id = tid; id < 256 * cpr; id += 256) {
-        const int rr = id / cpr, cc = id % cpr;
-        const int od = od0 + (rr >> 6), oh = oh0 + ((rr >> 3) & 7), ow = ow0 + (rr & 7);
-        const size_t vox = ((((((size_t)b << lo) + od) << lo) + oh) << lo) + ow;
-        *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(y) + vox * (CD_COUT * es) + nh * CDH_COUT * es + cc * 16) =
-            *reinterpret_cast<const uint4 *>(stage + rr * CDH_SP + cc * 16);
-    }
+    vv_direct_store_box<256, CDH_SP, CDH_COUT, CD_COUT>(stage, y, box, lo, tid, out_fp8);
 }
 
 
@@ -703,16 +567,11 @@ VV_EXPORT int vv_conv3d_k4s2_direct_fwd_io(const void *x, const void *w_packed, 
     if (!vv_aligned16(x) || !vv_aligned16(w_packed) || !vv_aligned16(y)) return VV_ERR_ALIGN;
     const int so = side / 2;
     const int boxes = (so / 4) * (so / 8) * (so / 8);
-    static const bool attr = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_direct_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CD_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_direct16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CD_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_direct16h_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CDH_LDS);
-        return true;
-    }();
-    (void)attr;
-    const char *se = vv_hook("VV_CD_SHAPE");          // 16 = v_mfma_f32_16x16x32_bf16 (default), 32 = v_mfma_f32_32x32x16_bf16, 8 = two 4-wave workgroups per CU
-    const bool s16 = !se || atoi(se) != 32;
-    const bool half = se && atoi(se) == 8;
+    vv_allow_lds<&conv_direct_kernel>(CD_LDS);
+    vv_allow_lds<&conv_direct16_kernel>(CD_LDS);
+    vv_allow_lds<&conv_direct16h_kernel>(CDH_LDS);
+    const int shape = vv_hook_int(vv_hook("VV_CD_SHAPE"), 16);    // 16 = v_mfma_f32_16x16x32_bf16 (default), 32 = v_mfma_f32_32x32x16_bf16, 8 = two 4-wave workgroups per CU
+    const bool s16 = shape != 32, half = shape == 8;
     const size_t in_per = (size_t)side * side * side * cin * 2, out_per = (size_t)so * so * so * cout * (out_dtype == VV_FP8 ? 1 : 2);
     const int per = vv_chunk_samples(in_per, batch);
     if (per < 1) return VV_ERR_SHAPE;
@@ -724,7 +583,7 @@ VV_EXPORT int vv_conv3d_k4s2_direct_fwd_io(const void *x, const void *w_packed, 
             VV_LAUNCH(conv_direct16h_kernel, dim3(nb * boxes * 2), dim3(256), CDH_LDS, reinterpret_cast<hipStream_t>(stream), xc,
                       reinterpret_cast<const __bf16 *>(w_packed), scale, shift, yc, vv_log2(so), (unsigned)((size_t)nb * in_per),
                       (unsigned)((size_t)64 * cin * cout * 2), act, out_dtype == VV_FP8 ? 1 : 0,
-                      vv_hook("VV_CDH_STAGGER") ? atoi(vv_hook("VV_CDH_STAGGER")) : 5, vv_hook("VV_CDH_ABL") ? atoi(vv_hook("VV_CDH_ABL")) : 0);
+                      vv_hook_int(vv_hook("VV_CDH_STAGGER"), 5), vv_hook_int(vv_hook("VV_CDH_ABL"), 0));
         else if (s16)
             VV_LAUNCH(conv_direct16_kernel, dim3(nb * boxes), dim3(512), CD_LDS, reinterpret_cast<hipStream_t>(stream), xc,
                       reinterpret_cast<const __bf16 *>(w_packed), scale, shift, yc, vv_log2(so), (unsigned)((size_t)nb * in_per),

@@ -9,18 +9,11 @@
 //     taps of the pair side by side in 128-byte rows (swizzle (row >> 1) & 7 as in the bf16 kernel);
 //   * operands of 32 bytes per lane: two adjacent slots, i.e. address and address ^ 16.
 // Output e4m3fn (for an fp8 consumer) or bf16.  Per-output-channel weight scales ride in `scale`.
-#include <type_traits>
-
-#include "common.h"
+#include "direct_common.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory");
-}
 
 constexpr int F8_CIN = 64, F8_COUT = 128;
 constexpr int F8_RB = F8_CIN;                     // bytes per voxel row
@@ -43,13 +36,8 @@ __global__ __launch_bounds__(512, 1) void conv_direct_fp8_kernel(const unsigned 
     const int wm = wave >> 1, wn = wave & 1;
     const int lo = dout_log2, no = 1 << lo, li = lo + 1, n = 1 << li;
 
-    const int nwg = gridDim.x;
-    int blk = (nwg & 7) == 0 ? (int)(blockIdx.x & 7) * (nwg >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    const int bxw = no >> 3, bxh = no >> 3, bxd = no >> 2;
-    const int bw = blk % bxw; blk /= bxw;
-    const int bh = blk % bxh; blk /= bxh;
-    const int bd = blk % bxd; const int b = blk / bxd;
-    const int od0 = bd * 4, oh0 = bh * 8, ow0 = bw * 8;
+    const VvDirectBox box = vv_direct_box(no);
+    const int b = box.b, od0 = box.od0, oh0 = box.oh0, ow0 = box.ow0;
 
     const u32x4 rsx = vv_make_rsrc(x, x_bytes), rsw = vv_make_rsrc(w, w_bytes);
     const unsigned lds0 = (unsigned)(unsigned long long)(lptr_t)smem;
@@ -89,7 +77,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct_fp8_kernel(const unsigned 
     issue_w(0);
     issue_w(1);
     issue_w(2);
-    wait_vm<0>();
+    vv_wait_vm<0>();
     __syncthreads();
 
     // ---- consumer addressing (LDS byte addresses); the second 16 bytes of a 32-byte operand sit at address ^ 16
@@ -174,7 +162,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct_fp8_kernel(const unsigned 
             // chunk c+1's weights (and, before the first tap of the next phase, the whole next tile) have landed.  Issued after
             // w(c+1): [the tile pieces of the previous chunk's slot: 2, 1, 1, 0 for J = 0..3] w(c+2) x2; chunk 3 also needs the
             // piece of chunk 2, which precedes w(c+2).
-            wait_vm<(J == 1) ? 4 : (J == 2 ? 3 : 2)>();
+            vv_wait_vm<(J == 1) ? 4 : (J == 2 ? 3 : 2)>();
             __syncthreads();
             __builtin_amdgcn_sched_barrier(0);
             F8_MF(Q, 0, 0);                        // second tap
@@ -196,7 +184,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct_fp8_kernel(const unsigned 
         chunk(std::integral_constant<int, 3>{});
     }
     F8_WAITFRAG(P, 0);                              // the look-ahead reads of the non-existent chunk 32
-    wait_vm<0>();                                   // trailing zero-fill pieces still target LDS
+    vv_wait_vm<0>();                                // trailing zero-fill pieces still target LDS
     __syncthreads();
 #undef F8_LDFRAG
 #undef F8_MF
@@ -223,57 +211,14 @@ __global__ __launch_bounds__(512, 1) void conv_direct_fp8_kernel(const unsigned 
 #pragma unroll
             for (int g = 0; g < 4; ++g) shv[nt][g] = *reinterpret_cast<const f32x4 *>(shift + wn * 64 + nt * 32 + 8 * g + 4 * fh);
     }
-    auto fill = [&](auto act_c, auto fp8_c) {
-        constexpr int ACT = decltype(act_c)::value;
-        constexpr bool FP8 = decltype(fp8_c)::value;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int c = wn * 64 + nt * 32 + 8 * g + 4 * fh;
-                    const f32x4 sc = scv[nt][g], sh = shv[nt][g];
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float t = acc[nt][mt][4 * g + e] * sc[e] + sh[e];
-                        if (ACT == VV_ACT_ELU) { const float em = __expf(fminf(t, 0.f)) - 1.f; t = t > 0.f ? t : em; }
-                        else if (ACT == VV_ACT_RELU) t = fmaxf(t, 0.f);
-                        else if (ACT == VV_ACT_LRELU) t = t > 0.f ? t : 0.3f * t;
-                        v[e] = t;
-                    }
-                    char *dst = stage + (wm * 64 + mt * 32 + fr) * F8_SP;
-                    if (FP8) {
-                        *reinterpret_cast<unsigned *>(dst + c) = vv_pack_fp8x4(v);
-                    } else {
-                        bf16x4 o;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] = static_cast<__bf16>(v[e]);
-                        *reinterpret_cast<bf16x4 *>(dst + c * 2) = o;
-                    }
-                }
-    };
+    auto fill = VV_DIRECT_FILL32(F8_SP, wn * 64);
     auto with_out = [&](auto act_c) {
         if (out_fp8) fill(act_c, std::true_type{});
         else fill(act_c, std::false_type{});
     };
-    switch (act) {
-        case VV_ACT_ELU: with_out(std::integral_constant<int, VV_ACT_ELU>{}); break;
-        case VV_ACT_RELU: with_out(std::integral_constant<int, VV_ACT_RELU>{}); break;
-        case VV_ACT_LRELU: with_out(std::integral_constant<int, VV_ACT_LRELU>{}); break;
-        default: with_out(std::integral_constant<int, VV_ACT_NONE>{}); break;
-    }
+    VV_WITH_ACT(act, with_out);
     __syncthreads();
-    const int es = out_fp8 ? 1 : 2;                   // the fp8 form hands the layer's output to an fp8 consumer (e4m3fn)
-    const int cpr = F8_COUT * es / 16;                // 16-byte chunks per output row
-    for (int id = tid; id < 256 * cpr; id += 512) {
-        const int r = id / cpr, cc = id % cpr;
-        const int od = od0 + (r >> 6), oh = oh0 + ((r >> 3) & 7), ow = ow0 + (r & 7);
-        const size_t vox = ((((((size_t)b << lo) + od) << lo) + oh) << lo) + ow;
-        *reinterpret_cast<uint4 *>(reinterpret_cast<char *>(y) + vox * (F8_COUT * es) + cc * 16) =
-            *reinterpret_cast<const uint4 *>(stage + r * F8_SP + cc * 16);
-    }
+    vv_direct_store_box<512, F8_SP, F8_COUT, F8_COUT>(stage, y, box, lo, tid, out_fp8);
 }
 
 }  // namespace
@@ -293,11 +238,7 @@ VV_EXPORT int vv_conv3d_k4s2_direct_fp8_fwd(const void *x, const void *w_packed,
     if (xb >= 0xFFFFFFF0ull) return VV_ERR_SHAPE;
     const int so = side / 2;
     const int boxes = (so / 4) * (so / 8) * (so / 8);
-    static const bool attr = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_direct_fp8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F8_LDS);
-        return true;
-    }();
-    (void)attr;
+    vv_allow_lds<&conv_direct_fp8_kernel>(F8_LDS);
     VV_LAUNCH(conv_direct_fp8_kernel, dim3(batch * boxes), dim3(512), F8_LDS, reinterpret_cast<hipStream_t>(stream),
               reinterpret_cast<const unsigned char *>(x), reinterpret_cast<const unsigned char *>(w_packed), scale, shift, y,
               vv_log2(so), (unsigned)xb, (unsigned)((size_t)64 * cin * cout), act, out_dtype == VV_FP8 ? 1 : 0);

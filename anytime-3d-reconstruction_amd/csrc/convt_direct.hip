@@ -14,10 +14,6 @@
 //                forms (2 parities per wave, 2 x 4 x 8 or 4 x 4 x 8 cells) remain selectable (VV_DIRECT_MT = 2 / 4);
 //                weights-first MFMA, lane = cell, registers walk channels
 //   epilogue   : folded BN + activation on float4 quads, wave-private LDS transpose, 16-byte stores of whole channel rows
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "common.h"
 
 namespace {
@@ -85,7 +81,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || MT == 4) ? 1 : 2) void convT_d
             const unsigned vo = ok ? (unsigned)((((((b << li) + id) << li) + ih) << li) + iw) * RB + g * 16 : 0xFFFFFFF0u;
             vv_dma16(rs, vo, lds0 + it * 1024);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vv_wait_vm<0>();
     }
     __syncthreads();
 
@@ -254,18 +250,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 || MT == 4) ? 1 : 2) void convT_d
     };
 #pragma unroll 1
     for (int pi = 0; pi < PPW; ++pi) {
-        switch (act) {
-            case VV_ACT_ELU: run_parity(std::integral_constant<int, VV_ACT_ELU>{}, pi); break;
-            case VV_ACT_RELU: run_parity(std::integral_constant<int, VV_ACT_RELU>{}, pi); break;
-            case VV_ACT_LRELU: run_parity(std::integral_constant<int, VV_ACT_LRELU>{}, pi); break;
-            default: run_parity(std::integral_constant<int, VV_ACT_NONE>{}, pi); break;
-        }
+        VV_WITH_ACT(act, run_parity, pi);
     }
-}
-
-inline int grid_1d(long n) {
-    long g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
 }
 
 }  // namespace
@@ -277,7 +263,7 @@ VV_EXPORT int vv_convT3d_k4s2_direct_supported(int side, int cin, int cout, int 
 VV_EXPORT int vv_pack_convT_k4s2_frag(const float *w_keras, void *packed, int cin, int cout, void *stream) {
     if (!w_keras || !packed) return VV_ERR_NULL;
     if (cin <= 0 || cout <= 0 || cin % 16 || cout % 32) return VV_ERR_SHAPE;
-    VV_LAUNCH(pack_convT_frag_kernel, dim3(grid_1d((long)64 * cin * cout)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_keras,
+    VV_LAUNCH(pack_convT_frag_kernel, dim3(vv_grid_1d((long)64 * cin * cout)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_keras,
               reinterpret_cast<__bf16 *>(packed), cin, cout);
     return vv_launch_status();
 }
@@ -289,19 +275,13 @@ VV_EXPORT int vv_convT3d_k4s2_direct_fwd(const void *x, const void *w_frag, cons
     if (!vv_aligned16(x) || !vv_aligned16(w_frag) || !vv_aligned16(y)) return VV_ERR_ALIGN;
     // variants: "2" = 2x4x8 cells, 4 waves x 2 parities, 2 workgroups / CU; "4" = 4x4x8 cells, 4 waves x 2 parities;
     // "8" = 4x4x8 cells, 8 waves x 1 parity (each weight fragment feeds 4 MFMAs, 2 waves / SIMD)
-    const char *sel_env = vv_hook("VV_DIRECT_MT");                       // read per call so that tests can cover every variant
-    const int sel = sel_env ? atoi(sel_env) : 8;
+    const int sel = vv_hook_int(vv_hook("VV_DIRECT_MT"), 8);                      // read per call so that tests can cover every variant
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     auto launch = [&](auto mt_c, auto nw_c) {
         constexpr int MT = decltype(mt_c)::value, NW = decltype(nw_c)::value;
         const int boxes = (side / MT) * (side / 4) * (side / 8);
         constexpr int LDS = (MT + 2) * HH * HW * 128 * 2 + NW * 32 * (64 * 2 + 16);
-        static const bool attr = [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&convT_direct_kernel<128, 64, MT, NW>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            return true;
-        }();
-        (void)attr;
+        vv_allow_lds<&convT_direct_kernel<128, 64, MT, NW>>(LDS);
         const size_t in_per = (size_t)side * side * side * cin * 2, out_per = (size_t)8 * side * side * side * cout * 2;
         const int per = vv_chunk_samples(in_per, batch);           // 32-bit buffer offsets: <= 2 GiB of input per launch
         for (int b0 = 0; b0 < batch && per > 0; b0 += per) {

@@ -11,8 +11,6 @@
 //     a tap is 2 k-steps instead of 8 and retires in half the matrix-pipe time of the bf16 form;
 //   * the output stored as bf16 (the last layer consumes bf16).
 // Per-output-channel weight scales ride in `scale` (folded into the BatchNorm scale by the caller).
-#include <type_traits>
-
 #include "common.h"
 
 namespace {
@@ -84,7 +82,7 @@ __global__ __launch_bounds__(F8_NW * 64, 1) void convT_direct_fp8_kernel(const u
             const unsigned vo = ok ? (unsigned)((((((b << li) + id) << li) + ih) << li) + iw) * RB + g * 16 : 0xFFFFFFF0u;
             vv_dma16(rs, vo, lds0 + it * 1024);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vv_wait_vm<0>();
     }
     __syncthreads();
 
@@ -240,17 +238,7 @@ __global__ __launch_bounds__(F8_NW * 64, 1) void convT_direct_fp8_kernel(const u
             __builtin_amdgcn_wave_barrier();
         }
     };
-    switch (act) {
-        case VV_ACT_ELU: finish(std::integral_constant<int, VV_ACT_ELU>{}); break;
-        case VV_ACT_RELU: finish(std::integral_constant<int, VV_ACT_RELU>{}); break;
-        case VV_ACT_LRELU: finish(std::integral_constant<int, VV_ACT_LRELU>{}); break;
-        default: finish(std::integral_constant<int, VV_ACT_NONE>{}); break;
-    }
-}
-
-inline int grid_1d(long n) {
-    long g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
+    VV_WITH_ACT(act, finish);
 }
 
 }  // namespace
@@ -263,7 +251,7 @@ VV_EXPORT int vv_pack_convT_k4s2_frag_fp8(const float *w_keras, void *packed, in
     if (!w_keras || !packed) return VV_ERR_NULL;
     if (cin <= 0 || cout <= 0 || cin % 64 || cout % 32) return VV_ERR_SHAPE;
     if (!vv_aligned16(w_keras) || !vv_aligned16(packed)) return VV_ERR_ALIGN;
-    VV_LAUNCH(pack_convT_frag_fp8_kernel, dim3(grid_1d((long)16 * cin * cout)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_keras,
+    VV_LAUNCH(pack_convT_frag_fp8_kernel, dim3(vv_grid_1d((long)16 * cin * cout)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_keras,
               reinterpret_cast<unsigned *>(packed), cin, cout);
     return vv_launch_status();
 }
@@ -278,12 +266,8 @@ VV_EXPORT int vv_convT3d_k4s2_direct_fp8_fwd(const void *x, const void *w_frag, 
     if (xb >= 0xFFFFFFF0ull) return VV_ERR_SHAPE;
     const int boxes = (side / F8_MT) * (side / 4) * (side / 8);
     constexpr int LDS = (F8_MT + 2) * HH * HW * 128 + F8_NW * 32 * (64 * 2 + 16);
-    static const bool attr = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&convT_direct_fp8_kernel<128, 64, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&convT_direct_fp8_kernel<128, 64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        return true;
-    }();
-    (void)attr;
+    vv_allow_lds<&convT_direct_fp8_kernel<128, 64, false>>(LDS);
+    vv_allow_lds<&convT_direct_fp8_kernel<128, 64, true>>(LDS);
     const unsigned char *xb8 = reinterpret_cast<const unsigned char *>(x);
     const uint4 *wf4 = reinterpret_cast<const uint4 *>(w_frag);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -20,9 +20,7 @@
 //   epilogue   : folded BN + activation in registers, bf16 pack, v_permlane32_swap pairs -> one 16-byte store per lane and
 //                pair of channel groups (guide T21): no LDS staging, so the next parity's weight chunks keep streaming
 //   grid       : batch x ps workgroups, ps = 1, 2, 4, 8 splits of the 8 parities (ps > 1 only to fill the chip at batch < 256)
-#include <stdlib.h>
 
-#include <type_traits>
 #include <utility>
 
 #include "common.h"
@@ -36,11 +34,6 @@ constexpr int CW_RING = CW_X;
 constexpr int CW_ZERO = CW_RING + CW_NST * CW_WST; // 155,648
 constexpr int CW_SS = CW_ZERO + 256;               // scale[64], shift[64]
 constexpr int CW_LDS = CW_SS + 512;                // 156,416 B
-
-template <int N>
-__device__ __forceinline__ void cw_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory");
-}
 
 #define CW_LD(F, X0, X1, WA)                                                                                                     \
     asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %6 offset:4096"          \
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(512, 1) void ctw_kernel(const __bf16 *__restrict__ 
         *reinterpret_cast<float *>(smem + CW_SS + ch * 4) = scale ? scale[ch] : 1.f;
         *reinterpret_cast<float *>(smem + CW_SS + 256 + ch * 4) = shift ? shift[ch] : 0.f;
     }
-    cw_wait_vm<0>();
+    vv_wait_vm<0>();
     __syncthreads();
 
     // ---- consumer addressing
@@ -208,8 +201,8 @@ __global__ __launch_bounds__(512, 1) void ctw_kernel(const __bf16 *__restrict__ 
             // parity's epilogue, that epilogue's 8 stores (between the pieces in the in-order counter).  The count is only right
             // while the epilogue issues AT LEAST 8 vector-memory instructions (fewer = this wait no longer covers the piece);
             // tests/test_isa_lint.py pins, on the generated code, how many waits a piece survives before one covers it.
-            if (J < 2 && pi > 0) cw_wait_vm<9>();
-            else cw_wait_vm<1>();
+            if (J < 2 && pi > 0) vv_wait_vm<9>();
+            else vv_wait_vm<1>();
             __builtin_amdgcn_s_barrier();
             issue_w(cw, stg);
             ++cw;
@@ -243,7 +236,7 @@ __global__ __launch_bounds__(512, 1) void ctw_kernel(const __bf16 *__restrict__ 
         epilogue(p);
     }
     CW_WAIT(P, 0);                                   // the look-ahead reads of the chunk after the last
-    cw_wait_vm<0>();                                 // the tail's pieces still target this workgroup's LDS
+    vv_wait_vm<0>();                                 // the tail's pieces still target this workgroup's LDS
 }
 
 
@@ -310,7 +303,7 @@ __global__ __launch_bounds__(512, 1) void ctw16_kernel(const __bf16 *__restrict_
         *reinterpret_cast<float *>(smem + CW_SS + ch * 4) = scale ? scale[ch] : 1.f;
         *reinterpret_cast<float *>(smem + CW_SS + 256 + ch * 4) = shift ? shift[ch] : 0.f;
     }
-    cw_wait_vm<0>();
+    vv_wait_vm<0>();
     __syncthreads();
 
     // ---- consumer addressing: lane = (r, q): row r of a 16-row fragment, k quarter q
@@ -417,8 +410,8 @@ __global__ __launch_bounds__(512, 1) void ctw16_kernel(const __bf16 *__restrict_
             CW16_MF(P, 3, 0); CW16_MF(P, 3, 1); CW16_MF(P, 3, 2); CW16_MF(P, 3, 3);
             CW16_SB;
             CW16_WAIT(Q, 0);
-            if (J < 2 && pi > 0) cw_wait_vm<9>();
-            else cw_wait_vm<1>();
+            if (J < 2 && pi > 0) vv_wait_vm<9>();
+            else vv_wait_vm<1>();
             __builtin_amdgcn_s_barrier();
             CW16_SB;
             CW16_MF(Q, 0, 0); CW16_MF(Q, 0, 1); CW16_SB;
@@ -461,7 +454,7 @@ __global__ __launch_bounds__(512, 1) void ctw16_kernel(const __bf16 *__restrict_
         epilogue(p);
     }
     CW16_WAIT(P, 0);
-    cw_wait_vm<0>();
+    vv_wait_vm<0>();
     if (STATS) {
         // lanes (r, q), r = 0..15, hold the same channels for different cells: sum over r, then over the waves through LDS (free now)
 #pragma unroll
@@ -573,7 +566,7 @@ __global__ __launch_bounds__(256, 1) void ctw4_kernel(const __bf16 *__restrict__
         *reinterpret_cast<float *>(smem + CW_SS + ch * 4) = scale ? scale[ch] : 1.f;
         *reinterpret_cast<float *>(smem + CW_SS + 256 + ch * 4) = shift ? shift[ch] : 0.f;
     }
-    cw_wait_vm<0>();
+    vv_wait_vm<0>();
     __syncthreads();
     // folded BatchNorm of this lane's channels 16 cot + 4 q .. + 3 for the channel-tile pair the epilogue is working on (cot = 2 c2,
     // 2 c2 + 1): re-read from LDS when the pair changes (twice per parity), by reads that the next k-step boundary's wait covers
@@ -770,8 +763,8 @@ __global__ __launch_bounds__(256, 1) void ctw4_kernel(const __bf16 *__restrict__
             // the next chunk's two pieces have landed: younger than them are this wave's two pieces of the chunk after it and, with the
             // epilogue riding along, one store per chunk (two since).  A smaller count is always safe; the first two chunks of a parity
             // follow chunks whose store count differs, so they take the strict form.  voxvae/isa_lint.py pins what a piece survives.
-            if (EPI && J >= 2 && !(C4_ABL & 1)) cw_wait_vm<4>();
-            else cw_wait_vm<2>();
+            if (EPI && J >= 2 && !(C4_ABL & 1)) vv_wait_vm<4>();
+            else vv_wait_vm<2>();
             if constexpr (!(C4_ABL & 2)) __builtin_amdgcn_s_barrier();
             C4_SB;
             if constexpr (!(C4_ABL & 4)) issue_w(cw, stg);
@@ -821,7 +814,7 @@ __global__ __launch_bounds__(256, 1) void ctw4_kernel(const __bf16 *__restrict__
     } else {
         c4_static_for<16>([&](auto u_c) { c4_static_for<32>([&](auto k_c) { epi_gap(accA, u_c, k_c, std::true_type{}); }); });
     }
-    cw_wait_vm<0>();                                 // the tail's pieces still target this workgroup's LDS
+    vv_wait_vm<0>();                                 // the tail's pieces still target this workgroup's LDS
 }
 
 
@@ -850,19 +843,14 @@ VV_EXPORT int vv_convT3d_k4s2_whole_fwd(const void *x, const void *w_skip, const
     }
     // VV_CTW_SHAPE (test hook): 16 = the eight-wave kernel on v_mfma_f32_16x16x32_bf16 (default), 32 = the eight-wave kernel on
     // v_mfma_f32_32x32x16_bf16, 4 = four waves / one per SIMD / epilogue in the MFMA gaps on 16x16x32 (measured slower)
-    const char *se = vv_hook("VV_CTW_SHAPE");
-    const int shape = se ? atoi(se) : 16;
+    const int shape = vv_hook_int(vv_hook("VV_CTW_SHAPE"), 16);
     const bool shape16 = shape != 32;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     auto launch = [&](auto act_c) {
         constexpr int ACT = decltype(act_c)::value;
-        static const bool attr = [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ctw_kernel<ACT>), hipFuncAttributeMaxDynamicSharedMemorySize, CW_LDS);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ctw16_kernel<ACT>), hipFuncAttributeMaxDynamicSharedMemorySize, CW_LDS);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ctw4_kernel<ACT>), hipFuncAttributeMaxDynamicSharedMemorySize, CW_LDS);
-            return true;
-        }();
-        (void)attr;
+        vv_allow_lds<&ctw_kernel<ACT>>(CW_LDS);
+        vv_allow_lds<&ctw16_kernel<ACT>>(CW_LDS);
+        vv_allow_lds<&ctw4_kernel<ACT>>(CW_LDS);
         if (shape != 16 && shape != 32)
             VV_LAUNCH(ctw4_kernel<ACT>, dim3((unsigned)batch * ps), dim3(256), CW_LDS, st, reinterpret_cast<const __bf16 *>(x),
                       reinterpret_cast<const __bf16 *>(w_skip), scale, shift, reinterpret_cast<__bf16 *>(y), 8 / ps);
@@ -873,12 +861,7 @@ VV_EXPORT int vv_convT3d_k4s2_whole_fwd(const void *x, const void *w_skip, const
             VV_LAUNCH(ctw_kernel<ACT>, dim3((unsigned)batch * ps), dim3(512), CW_LDS, st, reinterpret_cast<const __bf16 *>(x),
                       reinterpret_cast<const __bf16 *>(w_skip), scale, shift, reinterpret_cast<__bf16 *>(y), 8 / ps);
     };
-    switch (act) {
-        case VV_ACT_ELU: launch(std::integral_constant<int, VV_ACT_ELU>{}); break;
-        case VV_ACT_RELU: launch(std::integral_constant<int, VV_ACT_RELU>{}); break;
-        case VV_ACT_LRELU: launch(std::integral_constant<int, VV_ACT_LRELU>{}); break;
-        default: launch(std::integral_constant<int, VV_ACT_NONE>{}); break;
-    }
+    vv_with_act(act, launch);
     return vv_launch_status();
 }
 
@@ -892,11 +875,7 @@ VV_EXPORT int vv_convT3d_k4s2_whole_stats_fwd(const void *x, const void *w_skip,
     if (!vv_convT3d_k4s2_whole_supported(side, cin, cout, dtype) || batch <= 0) return VV_ERR_SHAPE;
     if (!vv_aligned16(x) || !vv_aligned16(w_skip) || !vv_aligned16(y) || !vv_aligned16(stats_partial)) return VV_ERR_ALIGN;
     if (stats_bytes < (size_t)batch * 2 * 64 * sizeof(float)) return VV_ERR_WORKSPACE;
-    static const bool attr = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ctw16_kernel<VV_ACT_NONE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CW_LDS);
-        return true;
-    }();
-    (void)attr;
+    vv_allow_lds<&ctw16_kernel<VV_ACT_NONE, true>>(CW_LDS);
     VV_LAUNCH((ctw16_kernel<VV_ACT_NONE, true>), dim3((unsigned)batch), dim3(512), CW_LDS, reinterpret_cast<hipStream_t>(stream),
               reinterpret_cast<const __bf16 *>(x), reinterpret_cast<const __bf16 *>(w_skip), nullptr, nullptr, reinterpret_cast<__bf16 *>(y), 8,
               stats_partial);

@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void final_bce_sweep_fp8_kernel(const unsig
         }
     };
 
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // plane 0
+    vv_wait_vm<0>();                                             // plane 0
     __syncthreads();                                             // ... the zeroed P_{-1} and the tap scales, for every wave
     // dequantisation factors of this lane's 16 taps: quad g = taps nt*32 + 8g + 4fh .. +3
     f32x4 tsv[4];
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void final_bce_sweep_fp8_kernel(const unsig
         float2 y;
         asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(y) : "v"(target + o) : "memory");
         stage(d + 2);
-        asm volatile("s_waitcnt vmcnt(3)" ::: "memory");         // plane d+1 (issued a step ago) has landed
+        vv_wait_vm<3>();                                         // plane d+1 (issued a step ago) has landed
         __syncthreads();                                         // ... for every wave; P_d is published
 
         f32x16 acc_next[2];
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void final_bce_sweep_fp8_kernel(const unsig
         oldh ^= 1;
         __syncthreads();      // every gather of P_d / P_{d-1} and every read of plane d+1 is done: publish d+1, refill its slot
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the last (all-zero) look-ahead planes
+    vv_wait_vm<0>();                                             // the last (all-zero) look-ahead planes
     bce = vv_wave_sum(bce); tp = vv_wave_sum(tp); fp = vv_wave_sum(fp); fn = vv_wave_sum(fn);
     if (lane == 0) { red[wv][0] = bce; red[wv][1] = tp; red[wv][2] = fp; red[wv][3] = fn; }
     __syncthreads();
@@ -197,11 +197,7 @@ __global__ __launch_bounds__(256, 2) void final_bce_sweep_fp8_kernel(const unsig
 // reduced by the caller's final_reduce pass).  Returns the number of partial blocks per sample.
 int vv_final_bce_sweep_fp8_launch(const void *x, const float *w_keras, const float *target, float *probs, float *logits, float *partials,
                                   int batch, int side, float gamma, float epsilon, hipStream_t st) {
-    static const bool attr = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&final_bce_sweep_fp8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, S8_LDS);
-        return true;
-    }();
-    (void)attr;
+    vv_allow_lds<&final_bce_sweep_fp8_kernel>(S8_LDS);
     const int ntile = (side / 8) * (side / 8);
     VV_LAUNCH(final_bce_sweep_fp8_kernel, dim3(ntile * batch), dim3(256), S8_LDS, st, reinterpret_cast<const unsigned char *>(x), w_keras, target,
               probs, logits, partials, vv_log2(side), (unsigned)((size_t)batch * side * side * side * F8B_CIN), gamma, epsilon);

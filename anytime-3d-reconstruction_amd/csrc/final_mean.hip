@@ -8,8 +8,6 @@
 // (<= 8 float32 grids per object) and final_mean_finish_kernel forms the mean and scores it.  Every sum runs in a fixed order that depends
 // on (K, side) only -- k ascending inside a slice, slices ascending, 1,024-voxel stats blocks in order -- and not on the number of objects
 // in the call: no float atomics, two runs are bit-identical, and an object's result does not depend on what it is batched with.
-#include <stdlib.h>
-
 #include "common.h"
 
 namespace {
@@ -261,7 +259,7 @@ __global__ __launch_bounds__(256, 2) void final_mean_sweep_kernel(const __bf16 *
         }
     };
 
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // step 0's plane
+    vv_wait_vm<0>();                                             // step 0's plane
     __syncthreads();
     f32x4 acc[2][2];
     mfma_plane(0, acc);
@@ -283,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void final_mean_sweep_kernel(const __bf16 *
             }
         stage(oldh, ks, ds);                                     // step t + 2 into the slot step t's MFMAs have left
         FM_NEXT_PLANE();
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");         // in flight: [step t+1 x4][step t+2 x4] -> step t + 1 has landed
+        vv_wait_vm<4>();                                         // in flight: [step t+1 x4][step t+2 x4] -> step t + 1 has landed
         __syncthreads();                                         // ... for every wave; Q of step t is published
 
         f32x4 acc_next[2][2];
@@ -318,7 +316,7 @@ __global__ __launch_bounds__(256, 2) void final_mean_sweep_kernel(const __bf16 *
         __syncthreads();      // every gather of Q and every read of the next plane is done: publish the next Q, refill its slot
     }
 #undef FM_NEXT_PLANE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the two (all-zero) look-ahead planes past the end
+    vv_wait_vm<0>();                                             // the two (all-zero) look-ahead planes past the end
 
     float *dst = a.part + (size_t)s * a.slice_stride;
     for (int j = 0; j < rng; ++j) {
@@ -441,11 +439,7 @@ VV_EXPORT int vv_convT3d_final_mean_fwd(const void *x, const float *w_keras, con
     a.nslices = p.nslices; a.samples = samples;
     a.gamma = gamma; a.epsilon = epsilon; a.inv_k = 1.0f / (float)samples;
     if (p.sweep) {
-        static const bool attr = [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&final_mean_sweep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ms_lds(16));
-            return true;
-        }();
-        (void)attr;
+        vv_allow_lds<&final_mean_sweep_kernel>((int)ms_lds(16));
         // 32-bit buffer offsets: <= 2 GiB of input per launch, cut by whole objects; every per-object tensor moves on by the same range
         const size_t in_per = (size_t)side * side * side * FM_CIN * 2 * samples;
         const int per = vv_chunk_samples(in_per, objects);
@@ -464,18 +458,10 @@ VV_EXPORT int vv_convT3d_final_mean_fwd(const void *x, const float *w_keras, con
     } else {
         const dim3 grid((unsigned)((side / 4) * (side / 4) * (side / 4)), (unsigned)(objects * p.nslices));
         if (dtype == VV_BF16) {
-            static const bool attr = [] {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&final_mean_box_kernel<__bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, FMB_LDS);
-                return true;
-            }();
-            (void)attr;
+            vv_allow_lds<&final_mean_box_kernel<__bf16>>(FMB_LDS);
             VV_LAUNCH(final_mean_box_kernel<__bf16>, grid, dim3(256), FMB_LDS, st, reinterpret_cast<const __bf16 *>(x), w_keras, a, vv_log2(side));
         } else {
-            static const bool attr = [] {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&final_mean_box_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, FMB_LDS);
-                return true;
-            }();
-            (void)attr;
+            vv_allow_lds<&final_mean_box_kernel<float>>(FMB_LDS);
             VV_LAUNCH(final_mean_box_kernel<float>, grid, dim3(256), FMB_LDS, st, reinterpret_cast<const float *>(x), w_keras, a, vv_log2(side));
         }
     }

@@ -1,10 +1,7 @@
 // The HBM-bound tail of the path (gfx950):
 //   final_bce  : Conv3DTranspose k4 s2 SAME -> 1 channel, sigmoid, weighted BCE and TP/FP/FN, fused
 //                (autoencoder3D.py:129-136; function.py:73-82, 100-115)
-#include <stdlib.h>
 #include <string.h>
-
-#include <type_traits>
 
 #include "common.h"
 
@@ -169,7 +166,7 @@ __global__ __launch_bounds__(256) void final_bce_mfma_kernel(const __bf16 *__res
         for (int e = 0; e < 4; ++e) { o[e] = static_cast<__bf16>(w0[e]); o[4 + e] = static_cast<__bf16>(w1[e]); }
         *reinterpret_cast<bf16x8 *>(Ws + fm_lds_off(row, slot)) = o;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vv_wait_vm<0>();
     __syncthreads();
 
     // MFMA: wave -> tap half nt = wv & 1, row tiles mt = (wv >> 1) + 2 j
@@ -367,7 +364,7 @@ __global__ __launch_bounds__(256, SW_DEPTH == 1 ? 3 : 2) void final_bce_sweep_ke
 
     // Software pipeline: step d publishes P_d (computed during step d-1) and then runs the MFMAs of plane d+1 in the same
     // instruction stream as the gather / loss math of plane d (matrix pipe under the VALU and LDS work).
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // plane 0
+    vv_wait_vm<0>();                                             // plane 0
     __syncthreads();                                             // ... for every wave
     f32x16 acc[2];
     mfma_plane(0, acc);
@@ -416,7 +413,7 @@ __global__ __launch_bounds__(256, SW_DEPTH == 1 ? 3 : 2) void final_bce_sweep_ke
         stage(d + 1 + SW_DEPTH, oldh);
         // depth 1: [plane d+1 x4][stores d-1][y d][plane d+2 x4] -> all but the newest 5.  depth 2: plane d+1 is followed by
         // stores d-2 (0..2), y d-1, plane d+2 x4, stores d-1 (0..2), y d, plane d+3 x4 = 10..14 operations -> all but the newest 10
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SW_DEPTH == 1 ? 5 : 10) : "memory");         // plane d+1 has landed
+        vv_wait_vm<SW_DEPTH == 1 ? 5 : 10>();                                                 // plane d+1 has landed
         __syncthreads();                                         // ... for every wave; P_d is published
 
         f32x16 acc_next[2];
@@ -463,7 +460,7 @@ __global__ __launch_bounds__(256, SW_DEPTH == 1 ? 3 : 2) void final_bce_sweep_ke
         oldh = nexth;
         __syncthreads();      // every gather of P_d / P_{d-1} and every read of plane d+1 is done: publish d+1, refill its slot
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the last (all-zero) look-ahead planes
+    vv_wait_vm<0>();                                             // the last (all-zero) look-ahead planes
     bce = vv_wave_sum(bce); tp = vv_wave_sum(tp); fp = vv_wave_sum(fp); fn = vv_wave_sum(fn);
     if (lane == 0) { red[wv][0] = bce; red[wv][1] = tp; red[wv][2] = fp; red[wv][3] = fn; }
     __syncthreads();
@@ -604,7 +601,7 @@ __global__ __launch_bounds__(256, 4) void final_bce_sweepw_kernel(const __bf16 *
 
     // Software pipeline: step d publishes Q_d (computed during step d-1) and then runs the MFMAs of plane d+1 in the same
     // instruction stream as the gather / loss math of plane d (matrix pipe under the VALU and LDS work).
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // plane 0
+    vv_wait_vm<0>();                                             // plane 0
     __syncthreads();                                             // ... for every wave
     f32x4 acc[2][2];
     mfma_plane(0, acc);
@@ -637,7 +634,7 @@ __global__ __launch_bounds__(256, 4) void final_bce_sweepw_kernel(const __bf16 *
         stage(d + 1 + SW_DEPTH, oldh);
         // depth 1: [plane d+1 x4][stores d-1][y d][plane d+2 x4] -> all but the newest 5.  depth 2: plane d+1 is followed by
         // stores d-2 (0..2), y d-1, plane d+2 x4, stores d-1 (0..2), y d, plane d+3 x4 = 10..14 operations -> all but the newest 10
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SW_DEPTH == 1 ? 5 : 10) : "memory");         // plane d+1 has landed
+        vv_wait_vm<SW_DEPTH == 1 ? 5 : 10>();                                                 // plane d+1 has landed
         __syncthreads();                                         // ... for every wave; Q_d is published
 
         f32x4 acc_next[2][2];
@@ -683,7 +680,7 @@ __global__ __launch_bounds__(256, 4) void final_bce_sweepw_kernel(const __bf16 *
         oldh = nexth;
         __syncthreads();      // every gather of Q_d and every read of plane d+1 is done: publish d+1, refill its slot
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the last (all-zero) look-ahead planes
+    vv_wait_vm<0>();                                             // the last (all-zero) look-ahead planes
     bce = vv_wave_sum(bce); tp = vv_wave_sum(tp); fp = vv_wave_sum(fp); fn = vv_wave_sum(fn);
     if (lane == 0) { red[wv][0] = bce; red[wv][1] = tp; red[wv][2] = fp; red[wv][3] = fn; }
     __syncthreads();
@@ -968,12 +965,7 @@ __global__ __launch_bounds__(256, 3) void first_conv_plane_kernel(const float *_
         }
     }
     };
-    switch (act) {
-        case VV_ACT_ELU: run(std::integral_constant<int, VV_ACT_ELU>{}); break;
-        case VV_ACT_RELU: run(std::integral_constant<int, VV_ACT_RELU>{}); break;
-        case VV_ACT_LRELU: run(std::integral_constant<int, VV_ACT_LRELU>{}); break;
-        default: run(std::integral_constant<int, VV_ACT_NONE>{}); break;
-    }
+    VV_WITH_ACT(act, run);
 }
 
 // first_conv, chained plane form (D = 32 or 64, bf16 or e4m3fn output, at least two consecutive items per workgroup).  One item =
@@ -1152,12 +1144,7 @@ __global__ __launch_bounds__(256, 4) void first_conv_chain_kernel(const float *_
         }
     }
     };
-    switch (act) {
-        case VV_ACT_ELU: run(std::integral_constant<int, VV_ACT_ELU>{}); break;
-        case VV_ACT_RELU: run(std::integral_constant<int, VV_ACT_RELU>{}); break;
-        case VV_ACT_LRELU: run(std::integral_constant<int, VV_ACT_LRELU>{}); break;
-        default: run(std::integral_constant<int, VV_ACT_NONE>{}); break;
-    }
+    VV_WITH_ACT(act, run);
 }
 
 __global__ __launch_bounds__(64) void final_reduce_kernel(const float *__restrict__ partials, float *__restrict__ stats, int nblk) {
@@ -1274,11 +1261,7 @@ int final_bce_impl(const void *x, const float *w_keras, const float *target, flo
     // "sweep" = the form with the w direction summed inside the MFMA (round 3); "sweepp" = the form that publishes P[halo cell][64 taps]
     const bool form_p = force && !strcmp(force, "sweepp");
     if (sweep) {
-        static const bool attr = [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&final_bce_sweep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SW_LDS);
-            return true;
-        }();
-        (void)attr;
+        vv_allow_lds<&final_bce_sweep_kernel>(SW_LDS);
         // 32-bit buffer offsets: <= 2 GiB of input per launch; every per-sample tensor moves on by the same sample range
         const size_t in_per = (size_t)side * side * side * FB_CIN * 2, vox = (size_t)8 * side * side * side;
         const int per = vv_chunk_samples(in_per, batch);
@@ -1322,7 +1305,7 @@ int vv_first_conv_bf16_launch(const float *x, const void *w_packed, const float 
         const size_t tile_b = ((size_t)4 * r * pd * 4 + 15) & ~(size_t)15;
         const size_t lds = tile_b + (out_fp8 ? (size_t)256 * (64 * 2) : tile_b) + 128 * sizeof(float) + 8 * 64 * 16;
         const int nslots = 4 * r * (side / 4), ni = (nslots + 255) / 256;
-        static const long envwg = vv_hook("VV_FIRSTCONV_WGS") ? atol(vv_hook("VV_FIRSTCONV_WGS")) : 0;
+        static const long envwg = vv_hook_int(vv_hook("VV_FIRSTCONV_WGS"), 0);
         // D = 32 / 64 and batches that give every workgroup a chain of >= 2 consecutive output planes: the chained kernel, FOUR persistent
         // workgroups per CU (D = 32, batch 256: 4,096 items = 1,024 x 4); its input offsets are 32-bit (< 2 GiB of input per launch)
         const bool nochain = vv_hook("VV_FIRSTCONV_NOCHAIN") != nullptr;      // test hook: the plane form at every batch

@@ -19,10 +19,6 @@
 // through the STAGES parameter but measured slower than 2 stages x 2 workgroups per CU).  Small grids run position-major
 // with per-tile tap lists (padded taps skipped); work is ordered XCD-aware.  Split-K writes f32 slabs that
 // igemm_splitk_epilogue sums in a fixed order (deterministic).
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "common.h"
 
 int vv_first_conv_bf16_launch(const float *x, const void *w_packed, const float *scale, const float *shift, void *y, int batch,
@@ -436,9 +432,9 @@ __global__ __launch_bounds__(256 * KH) void igemm_kernel(const IgemmArgs a) {
         int st = 0;
         for (int i = 0; i < nv; ++i) {
             const int younger = min(STAGES - 2, nv - 1 - i);
-            if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPC) : "memory");
-            else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPC) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (younger >= 2) vv_wait_vm<2 * LPC>();
+            else if (younger == 1) vv_wait_vm<LPC>();
+            else vv_wait_vm<0>();
             __syncthreads();
             if (i + STAGES - 1 < nv) issue(vb + i + STAGES - 1, st == 0 ? STAGES - 1 : st - 1);
             compute(st);
@@ -450,13 +446,13 @@ __global__ __launch_bounds__(256 * KH) void igemm_kernel(const IgemmArgs a) {
         const int nsteps = (ve - vb + 1) >> 1;
         auto issue_step = [&](int i, int buf) { const int v = vb + 2 * i + half; issue(v < ve ? v : vb, buf, v < ve); };
         if (nsteps > 0) issue_step(0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vv_wait_vm<0>();
         __syncthreads();
         int buf = 0;
         for (int i = 0; i < nsteps; ++i) {
             if (i + 1 < nsteps) issue_step(i + 1, buf ^ 1);
             compute(buf);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            vv_wait_vm<0>();
             __syncthreads();
             buf ^= 1;
         }
@@ -490,7 +486,7 @@ __global__ __launch_bounds__(256 * KH) void igemm_kernel(const IgemmArgs a) {
             if constexpr (DMA) issue(vi, 0);
             else { gload(vi); lstore(0); }
         }
-        if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (DMA) vv_wait_vm<0>();
         __syncthreads();
         int buf = 0;
         for (; vi < ve; ++vi) {
@@ -501,7 +497,7 @@ __global__ __launch_bounds__(256 * KH) void igemm_kernel(const IgemmArgs a) {
             }
             compute(buf);
             if (more) lstore(buf ^ 1);
-            if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // chunk vi+1 has landed (it flew during the MFMAs)
+            if constexpr (DMA) vv_wait_vm<0>();                                   // chunk vi+1 has landed (it flew during the MFMAs)
             __syncthreads();
             buf ^= 1;
         }
@@ -583,12 +579,7 @@ __global__ __launch_bounds__(256 * KH) void igemm_kernel(const IgemmArgs a) {
         else if (okind == 3) fill(act_c, std::integral_constant<int, 3>{});
         else fill(act_c, std::integral_constant<int, 2>{});
     };
-    switch (a.partial ? VV_ACT_NONE : a.act) {
-        case VV_ACT_ELU: with_kind(std::integral_constant<int, VV_ACT_ELU>{}); break;
-        case VV_ACT_RELU: with_kind(std::integral_constant<int, VV_ACT_RELU>{}); break;
-        case VV_ACT_LRELU: with_kind(std::integral_constant<int, VV_ACT_LRELU>{}); break;
-        default: with_kind(std::integral_constant<int, VV_ACT_NONE>{}); break;
-    }
+    VV_WITH_ACT(a.partial ? VV_ACT_NONE : a.act, with_kind);
     __syncthreads();
     const int cpr = BN * es / 16;  // 16-byte chunks per tile row
     char *outb = a.partial ? reinterpret_cast<char *>(a.partial) : reinterpret_cast<char *>(a.Out);
@@ -658,11 +649,11 @@ Plan make_plan(int mode, int M, int N, int K, int dtype) {
     const int bk = dtype == VV_BF16 ? 64 : (dtype == VV_FP8 ? 128 : 32);
     const int nchunks = (K + bk - 1) / bk;
     const long tiles = (long)((M + p.bm - 1) / p.bm) * ((N + p.bn - 1) / p.bn) * p.nparity;
-    static const long target = vv_hook("VV_SPLIT_TARGET") ? atol(vv_hook("VV_SPLIT_TARGET")) : 512;
+    static const long target = vv_hook_int(vv_hook("VV_SPLIT_TARGET"), 512);
     int split = 1;
     // at least 8 chunks per share -- 4 when the tile grid is a handful of workgroups (the Dense-shaped layers at batch
     // 256: 2 tiles x K = 4096 ran as 8 workgroups of 16 dependent chunks, a latency chain of 18 us)
-    static const int min_chunks_small = vv_hook("VV_SPLIT_MINCHUNKS") ? atoi(vv_hook("VV_SPLIT_MINCHUNKS")) : 4;
+    static const int min_chunks_small = vv_hook_int(vv_hook("VV_SPLIT_MINCHUNKS"), 4);
     const int min_chunks = tiles <= 8 ? min_chunks_small : 8;
     while (tiles * split < target && split * 2 <= nchunks / min_chunks && split < 64) split *= 2;
     // The first factor of two is taken INSIDE the workgroup (two 4-wave halves on alternate chunks, accumulators handed
@@ -678,8 +669,8 @@ Plan make_plan(int mode, int M, int N, int K, int dtype) {
 
 // Position-major rows pay off where a large share of the taps is padding (small grids) and the batch fills tiles.
 bool use_pos_major(int mode, int din, int batch) {
-    static const int conv_max = vv_hook("VV_POSMAJOR_CONV_SIDE") ? atoi(vv_hook("VV_POSMAJOR_CONV_SIDE")) : 8;
-    static const int convT_max = vv_hook("VV_POSMAJOR_CONVT_SIDE") ? atoi(vv_hook("VV_POSMAJOR_CONVT_SIDE")) : 4;
+    static const int conv_max = vv_hook_int(vv_hook("VV_POSMAJOR_CONV_SIDE"), 8);
+    static const int convT_max = vv_hook_int(vv_hook("VV_POSMAJOR_CONVT_SIDE"), 4);
     if (batch < 32) return false;
     if (mode == MODE_CONV) return din <= conv_max;
     if (mode == MODE_CONVT) return din <= convT_max;
@@ -691,12 +682,7 @@ void launch_k(const IgemmArgs &a, dim3 grid, hipStream_t st) {
     constexpr size_t stage_bytes = (size_t)KH * STAGES * (128 + BN) * ROWB + 272;   // staging of every half + tap list
     constexpr size_t epi_bytes = (size_t)128 * (BN * 4 + 16);
     constexpr size_t lds = stage_bytes > epi_bytes ? stage_bytes : epi_bytes;
-    static const bool attr_set = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&igemm_kernel<T, MODE, 128, BN, STAGES, KH>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        return true;
-    }();
-    (void)attr_set;
+    vv_allow_lds<&igemm_kernel<T, MODE, 128, BN, STAGES, KH>>((int)lds);
     VV_LAUNCH((igemm_kernel<T, MODE, 128, BN, STAGES, KH>), grid, dim3(256 * KH), lds, st, a);
 }
 
@@ -704,7 +690,7 @@ template <typename T, int MODE>
 int launch_t(const IgemmArgs &a, const Plan &p, hipStream_t st) {
     const int tiles = ((a.M + p.bm - 1) / p.bm) * ((a.N + p.bn - 1) / p.bn);
     dim3 grid(tiles * p.split * p.nparity);
-    static const int stages_env = vv_hook("VV_STAGES") ? atoi(vv_hook("VV_STAGES")) : 2;
+    static const int stages_env = vv_hook_int(vv_hook("VV_STAGES"), 2);
     const int stages = (MODE == MODE_FIRST || sizeof(T) == 4) ? 2 : stages_env;   // deep ring: bf16 LDS-DMA modes only
     if (p.kh == 2) {
         if constexpr (MODE != MODE_FIRST) {
@@ -723,12 +709,7 @@ int launch_t(const IgemmArgs &a, const Plan &p, hipStream_t st) {
     if (p.split > 1) {
         const size_t total = (size_t)p.nparity * a.M * (a.N / 4);
         const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        switch (a.act) {
-            case VV_ACT_ELU: VV_LAUNCH((igemm_splitk_epilogue<MODE, VV_ACT_ELU>), dim3(blocks), dim3(256), 0, st, a, p.split, p.nparity); break;
-            case VV_ACT_RELU: VV_LAUNCH((igemm_splitk_epilogue<MODE, VV_ACT_RELU>), dim3(blocks), dim3(256), 0, st, a, p.split, p.nparity); break;
-            case VV_ACT_LRELU: VV_LAUNCH((igemm_splitk_epilogue<MODE, VV_ACT_LRELU>), dim3(blocks), dim3(256), 0, st, a, p.split, p.nparity); break;
-            default: VV_LAUNCH((igemm_splitk_epilogue<MODE, VV_ACT_NONE>), dim3(blocks), dim3(256), 0, st, a, p.split, p.nparity); break;
-        }
+        vv_with_act(a.act, [&](auto act_c) { VV_LAUNCH((igemm_splitk_epilogue<MODE, decltype(act_c)::value>), dim3(blocks), dim3(256), 0, st, a, p.split, p.nparity); });
     }
     return vv_launch_status();
 }

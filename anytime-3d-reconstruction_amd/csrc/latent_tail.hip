@@ -15,10 +15,6 @@
 //                  tiles (v_mfma_f32_16x16x32_bf16, weights straight from global memory: they are read once per workgroup),
 //                  folded BN + activation in the epilogues.  The first three steps are recomputed by every slice's workgroup
 //                  (a few thousand FLOPs) instead of being exchanged.
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "common.h"
 
 namespace {
@@ -73,7 +69,7 @@ __global__ __launch_bounds__(256) void lt_e5_kernel(const LtArgs a) {
             if (r8 < 16) vv_dma16(rsa, vo, dst);
             else vv_dma16(rsw, vo, dst);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vv_wait_vm<0>();
         __syncthreads();
 #pragma unroll
         for (int ch = 0; ch < 4; ++ch) {
@@ -402,7 +398,7 @@ struct LtPlan { int kslice, nslice, nq; size_t ws; };
 
 LtPlan lt_plan(int batch, int K5, int E, int n1) {
     LtPlan p;
-    static const int ks_env = vv_hook("VV_LT_KSLICE") ? atoi(vv_hook("VV_LT_KSLICE")) : 0;
+    static const int ks_env = vv_hook_int(vv_hook("VV_LT_KSLICE"), 0);
     int ks = (K5 + 31) / 32;                               // at most 32 slices
     if (ks_env > ks) ks = ks_env;
     ks = ((ks + LT_KS - 1) / LT_KS) * LT_KS;
@@ -425,12 +421,7 @@ int lt_launch_mid(const float *slabs, int nslice, int nq, const float *e5_scale,
     m.batch = batch; m.E = E; m.L = L; m.lin = lin; m.n1 = n1; m.nslice = nslice; m.nq = nq; m.variational = variational; m.act = act;
     const size_t lds = (size_t)16 * E * 4 + (size_t)16 * L * 2 + (size_t)16 * lin * 2;
     const dim3 grid(((batch + 15) / 16) * nq);
-    switch (act) {
-        case VV_ACT_ELU: VV_LAUNCH(lt_mid_kernel<VV_ACT_ELU>, grid, dim3(256), lds, st, m); break;
-        case VV_ACT_RELU: VV_LAUNCH(lt_mid_kernel<VV_ACT_RELU>, grid, dim3(256), lds, st, m); break;
-        case VV_ACT_LRELU: VV_LAUNCH(lt_mid_kernel<VV_ACT_LRELU>, grid, dim3(256), lds, st, m); break;
-        default: VV_LAUNCH(lt_mid_kernel<VV_ACT_NONE>, grid, dim3(256), lds, st, m); break;
-    }
+    vv_with_act(act, [&](auto act_c) { VV_LAUNCH(lt_mid_kernel<decltype(act_c)::value>, grid, dim3(256), lds, st, m); });
     return vv_launch_status();
 }
 
@@ -462,11 +453,7 @@ VV_EXPORT int vv_latent_tail_fwd(const void *h, const void *w5, const float *e5_
     const LtPlan p = lt_plan(batch, K5, E, n1);
     if (!workspace || workspace_bytes < p.ws || !vv_aligned16(workspace)) return VV_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    static const bool attr = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&lt_e5_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LT_E5_LDS);
-        return true;
-    }();
-    (void)attr;
+    vv_allow_lds<&lt_e5_kernel>(LT_E5_LDS);
     LtArgs a;
     a.h = h; a.w5 = w5; a.slabs = reinterpret_cast<float *>(workspace);
     a.batch = batch; a.K5 = K5; a.E = E; a.kslice = p.kslice; a.nslice = p.nslice;
@@ -519,12 +506,7 @@ VV_EXPORT int vv_conv_pos_latent_tail_fwd(const void *x4, const void *w4_skip, c
     a.batch = batch; a.cout4 = cout4; a.E = E; a.nh = nh; a.mtiles = plan.mtiles; a.rows_per_tile = plan.rows_per_tile; a.ntn = plan.ntn; a.act = act;
     for (int p = 0; p < 8; ++p) { a.nsplit[p] = plan.nsplit[p]; a.first[p] = plan.first[p]; }
     const dim3 grid(((batch + 15) / 16) * nslice);
-    switch (act) {
-        case VV_ACT_ELU: VV_LAUNCH(lt_e5x_kernel<VV_ACT_ELU>, grid, dim3(256), 0, st, a); break;
-        case VV_ACT_RELU: VV_LAUNCH(lt_e5x_kernel<VV_ACT_RELU>, grid, dim3(256), 0, st, a); break;
-        case VV_ACT_LRELU: VV_LAUNCH(lt_e5x_kernel<VV_ACT_LRELU>, grid, dim3(256), 0, st, a); break;
-        default: VV_LAUNCH(lt_e5x_kernel<VV_ACT_NONE>, grid, dim3(256), 0, st, a); break;
-    }
+    vv_with_act(act, [&](auto act_c) { VV_LAUNCH(lt_e5x_kernel<decltype(act_c)::value>, grid, dim3(256), 0, st, a); });
     rc = vv_launch_status();
     if (rc != VV_OK) return rc;
     int nq = 1;

@@ -23,10 +23,6 @@
 //               contiguous)
 //   order     : the shares and channel tiles of one position are neighbours in the XCD-aware work order (they read the same
 //               activation rows)
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "common.h"
 
 namespace {
@@ -207,8 +203,8 @@ __global__ __launch_bounds__(512, 1) void pg_kernel(const PgArgs a) {
     // ---- pipeline: chunk i lives in ring buffer i % 3; chunks i + 1 and i + 2 are in flight while i is multiplied
     if (nmine > 0) issue(0);
     if (nmine > 1) issue(1);
-    if (nmine > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPC) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (nmine > 1) vv_wait_vm<LPC>();
+    else vv_wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     if (nmine > 2) issue(2);
     pg_u4 P[4], Q[4];
@@ -228,8 +224,8 @@ __global__ __launch_bounds__(512, 1) void pg_kernel(const PgArgs a) {
         mma(P);
         PG_WAIT4(0, Q);
         // chunk i + 1 has landed (chunk i + 2, issued after it, may still fly); behind the barrier buffer `buf` is free
-        if (i + 2 < nmine) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPC) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (i + 2 < nmine) vv_wait_vm<LPC>();
+        else vv_wait_vm<0>();
         __builtin_amdgcn_s_barrier();
         if (i + 3 < nmine) issue(buf);
         buf = buf == PG_NST - 1 ? 0 : buf + 1;
@@ -298,12 +294,7 @@ __global__ __launch_bounds__(512, 1) void pg_kernel(const PgArgs a) {
             }
     };
     if (final_out) {
-        switch (a.act) {
-            case VV_ACT_ELU: fill(std::integral_constant<int, VV_ACT_ELU>{}, std::true_type{}); break;
-            case VV_ACT_RELU: fill(std::integral_constant<int, VV_ACT_RELU>{}, std::true_type{}); break;
-            case VV_ACT_LRELU: fill(std::integral_constant<int, VV_ACT_LRELU>{}, std::true_type{}); break;
-            default: fill(std::integral_constant<int, VV_ACT_NONE>{}, std::true_type{}); break;
-        }
+        VV_WITH_ACT(a.act, fill, std::true_type{});
     } else {
         fill(std::integral_constant<int, VV_ACT_NONE>{}, std::false_type{});
     }
@@ -380,7 +371,7 @@ void pg_plan(PgArgs &a, int batch, int cin, int cout) {
         chunks[p] = pg_axis<MODE>(od).cnt * pg_axis<MODE>(oh).cnt * pg_axis<MODE>(ow).cnt * NC;
         total += chunks[p];
     }
-    static const int target_env = vv_hook("VV_PG_TARGET") ? atoi(vv_hook("VV_PG_TARGET")) : 0;
+    static const int target_env = vv_hook_int(vv_hook("VV_PG_TARGET"), 0);
     long avg = (total * a.ntn * a.mtiles + 255) / 256;
     int target = (int)((avg + NC - 1) / NC) * NC;
     if (target < 8) target = 8;
@@ -407,11 +398,7 @@ size_t pg_ws_bytes(int batch, int cin, int cout) {
 template <int MODE>
 int pg_run(const void *x, const void *w, const float *scale, const float *shift, void *y, int batch, int cin, int cout, int act, void *ws,
            size_t ws_bytes, hipStream_t st) {
-    static const bool attr = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&pg_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, PG_LDS);
-        return true;
-    }();
-    (void)attr;
+    vv_allow_lds<&pg_kernel<MODE>>(PG_LDS);
     constexpr int VIN = MODE == 0 ? 64 : 8, VOUT = MODE == 0 ? 8 : 64;
     const size_t sample_in = (size_t)VIN * cin * 2, sample_out = (size_t)VOUT * cout * 2;
     int per = (int)((0x7FFFFFFFull / sample_in) / PG_BM) * PG_BM;        // 32-bit buffer offsets: <= 2 GiB of input per launch
@@ -438,12 +425,7 @@ int pg_run(const void *x, const void *w, const float *scale, const float *shift,
         if (any) {
             const size_t total = (size_t)a.npos * nb * (cout / 4);
             const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-            switch (act) {
-                case VV_ACT_ELU: VV_LAUNCH((pg_reduce_kernel<MODE, VV_ACT_ELU>), dim3(blocks), dim3(256), 0, st, a); break;
-                case VV_ACT_RELU: VV_LAUNCH((pg_reduce_kernel<MODE, VV_ACT_RELU>), dim3(blocks), dim3(256), 0, st, a); break;
-                case VV_ACT_LRELU: VV_LAUNCH((pg_reduce_kernel<MODE, VV_ACT_LRELU>), dim3(blocks), dim3(256), 0, st, a); break;
-                default: VV_LAUNCH((pg_reduce_kernel<MODE, VV_ACT_NONE>), dim3(blocks), dim3(256), 0, st, a); break;
-            }
+            vv_with_act(act, [&](auto act_c) { VV_LAUNCH((pg_reduce_kernel<MODE, decltype(act_c)::value>), dim3(blocks), dim3(256), 0, st, a); });
             rc = vv_launch_status();
             if (rc != VV_OK) return rc;
         }
@@ -468,11 +450,7 @@ size_t vv_pg_conv_slab_bytes(int batch, int cin, int cout) {
 }
 
 int vv_pg_conv_slabs(const void *x, const void *w, int batch, int cin, int cout, void *ws, size_t ws_bytes, hipStream_t st, VvPgSlabPlan *plan) {
-    static const bool attr = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&pg_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, PG_LDS);
-        return true;
-    }();
-    (void)attr;
+    vv_allow_lds<&pg_kernel<0>>(PG_LDS);
     const size_t need = vv_pg_conv_slab_bytes(batch, cin, cout);
     if (!need) return VV_ERR_SHAPE;
     if (!ws || ws_bytes < need || !vv_aligned16(ws)) return VV_ERR_WORKSPACE;

@@ -26,10 +26,6 @@
 //               during the previous unit; fragment reads are inline asm one step ahead of their MFMAs with counted lgkmcnt.
 //   workgroups: (batch / 4) x (Cout / 64) for conv, (batch / 4) x 4 parity pairs x (Cout / 128) for convT; ordered so that
 //               the groups of one sample quad run on one XCD.
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "common.h"
 
 namespace {
@@ -311,7 +307,7 @@ __global__ __launch_bounds__(512, 1) void sd_kernel(const SdArgs a) {
     issue_w(0, 0, 0);
     if (ntiles > 1) issue_a(1, q1_, c1_); else issue_a(0, 0, 0);   // (a single-tile layer re-stages tile 0: the count below stays fixed)
     issue_w(1, 0, 0);                                       // unit 1: conv (tile 0, ad 1) / convT (chunk 0, tap 1)
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");        // A(0), W(0) landed; A(1), W(1) (4 pieces each, younger) may fly on
+    vv_wait_vm<8>();                                        // A(0), W(0) landed; A(1), W(1) (4 pieces each, younger) may fly on
     __builtin_amdgcn_s_barrier();
 
     // zero target of an out-of-grid w lane: the bank position of the (wrapped) row it would have read -> conflict-free
@@ -374,7 +370,7 @@ __global__ __launch_bounds__(512, 1) void sd_kernel(const SdArgs a) {
                 SD_WAIT8(0, xP, wP);
                 SD_MMA_RD(xP, wP, 0, dm0 & hm1, SD_CONV_RDX(0, 3, xQ), SD_CONV_RDW(0, 3, wQ));
                 SD_WAIT8(0, xQ, wQ);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                vv_wait_vm<0>();
                 __builtin_amdgcn_s_barrier();
                 SD_MMA_RD(xQ, wQ, 0, dm0 & hm1, if (u + 2 < nunits) issue_w(u + 2, qb, cb); SD_CONV_RDX(1, 0, xP), SD_CONV_RDW(1, 0, wP));
             }
@@ -388,7 +384,7 @@ __global__ __launch_bounds__(512, 1) void sd_kernel(const SdArgs a) {
                 SD_WAIT8(0, xP, wP);
                 SD_MMA_RD(xP, wP, 0, dm1 & hm1, SD_CONV_RDX(1, 3, xQ), SD_CONV_RDW(1, 3, wQ));
                 SD_WAIT8(0, xQ, wQ);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                vv_wait_vm<0>();
                 __builtin_amdgcn_s_barrier();
                 const int lastmask = dm1 & hm1;
                 mma4(xQ, wQ, 0, lastmask, std::integral_constant<int, 0>{});
@@ -466,7 +462,7 @@ __global__ __launch_bounds__(512, 1) void sd_kernel(const SdArgs a) {
                 SD_WAIT8(0, xQ, wP);
                 SD_MMA_RD(xQ, wP, 0, vm, SD_T_W(A, wbt1, 1, wQ), (void)0);
                 SD_WAIT8(0, xQ, wQ);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                vv_wait_vm<0>();
                 __builtin_amdgcn_s_barrier();
                 mma4(xQ, wQ, 4, vm, std::integral_constant<int, 0>{});
                 if (u + 2 < nunits) issue_w(u + 2, 0, 0);
@@ -549,12 +545,7 @@ __global__ __launch_bounds__(512, 1) void sd_kernel(const SdArgs a) {
                 }
             }
         };
-        switch (a.act) {
-            case VV_ACT_ELU: fill(std::integral_constant<int, VV_ACT_ELU>{}); break;
-            case VV_ACT_RELU: fill(std::integral_constant<int, VV_ACT_RELU>{}); break;
-            case VV_ACT_LRELU: fill(std::integral_constant<int, VV_ACT_LRELU>{}); break;
-            default: fill(std::integral_constant<int, VV_ACT_NONE>{}); break;
-        }
+        VV_WITH_ACT(a.act, fill);
         __syncthreads();
         // 256 rows x 128 B leave as 16-byte pieces: 8 lanes per output row
 #pragma unroll
@@ -607,28 +598,14 @@ __global__ __launch_bounds__(512, 1) void sd_kernel(const SdArgs a) {
                 __builtin_amdgcn_wave_barrier();
             }
         };
-        switch (a.act) {
-            case VV_ACT_ELU: fill(std::integral_constant<int, VV_ACT_ELU>{}); break;
-            case VV_ACT_RELU: fill(std::integral_constant<int, VV_ACT_RELU>{}); break;
-            case VV_ACT_LRELU: fill(std::integral_constant<int, VV_ACT_LRELU>{}); break;
-            default: fill(std::integral_constant<int, VV_ACT_NONE>{}); break;
-        }
+        VV_WITH_ACT(a.act, fill);
     }
-}
-
-inline int sd_grid_1d(long n) {
-    long g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
 }
 
 template <int MODE>
 int sd_launch(const void *x, const void *w, const float *scale, const float *shift, void *y, int batch, int cin, int cout, int act,
               hipStream_t st) {
-    static const bool attr = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sd_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, SD_LDS);
-        return true;
-    }();
-    (void)attr;
+    vv_allow_lds<&sd_kernel<MODE>>(SD_LDS);
     const size_t in_vox = MODE == 0 ? 512 : 64, out_vox = MODE == 0 ? 64 : 512;
     const size_t sample_in = in_vox * cin * 2, sample_out = out_vox * cout * 2;
     // 32-bit buffer offsets: a launch covers at most 2 GiB of input; larger batches go out as several launches (sample quads
@@ -670,7 +647,7 @@ VV_EXPORT int vv_pack_conv_k4_skip(const float *w_keras, void *packed, int cin, 
         VV_LAUNCH(sd_pack_conv_tiled_kernel, dim3(64 * (cin / 64), cout / 64), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_keras,
                   reinterpret_cast<__bf16 *>(packed), cin, cout);
     else
-        VV_LAUNCH(sd_pack_conv_kernel, dim3(sd_grid_1d((long)64 * cin * cout)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_keras,
+        VV_LAUNCH(sd_pack_conv_kernel, dim3(vv_grid_1d((long)64 * cin * cout)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_keras,
                   reinterpret_cast<__bf16 *>(packed), cin, cout);
     return vv_launch_status();
 }
@@ -679,7 +656,7 @@ VV_EXPORT int vv_pack_convT_k4s2_skip(const float *w_keras, void *packed, int ci
     if (!w_keras || !packed) return VV_ERR_NULL;
     if (cin <= 0 || cout <= 0 || cin % 64) return VV_ERR_SHAPE;
     if (!vv_aligned16(w_keras) || !vv_aligned16(packed)) return VV_ERR_ALIGN;
-    VV_LAUNCH(sd_pack_convT_kernel, dim3(sd_grid_1d((long)8 * cin * cout)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_keras,
+    VV_LAUNCH(sd_pack_convT_kernel, dim3(vv_grid_1d((long)8 * cin * cout)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_keras,
               reinterpret_cast<__bf16 *>(packed), cin, cout);
     return vv_launch_status();
 }
@@ -713,7 +690,7 @@ VV_EXPORT int vv_pack_skip_images(const int *kinds, const float *const *w_keras,
             if (kinds[j] != kind) continue;
             const int n = t.njobs;
             t.w[n] = w_keras[j]; t.out[n] = reinterpret_cast<__bf16 *>(packed[j]); t.cin[n] = cin[j]; t.cout[n] = cout[j];
-            const int blocks = kind == 0 ? 64 * (cin[j] / 64) * (cout[j] / 64) : sd_grid_1d((long)8 * cin[j] * cout[j]);
+            const int blocks = kind == 0 ? 64 * (cin[j] / 64) * (cout[j] / 64) : vv_grid_1d((long)8 * cin[j] * cout[j]);
             t.first[n + 1] = t.first[n] + blocks;
             t.njobs = n + 1;
             if (t.njobs == SD_MAXJOBS) flush();

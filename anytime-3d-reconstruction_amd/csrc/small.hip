@@ -282,11 +282,6 @@ __global__ __launch_bounds__(64) void shape_metrics_kernel(const float *__restri
     }
 }
 
-inline int grid_for(size_t total) {
-    size_t g = (total + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
-
 // Bit-packed occupancy storage: voxel v of a sample is bit (v & 7) of byte v >> 3 (numpy
 // packbits, bitorder='little').  unpack: one thread per byte -> 8 floats (two 16-byte stores), rows gathered through idx.
 __global__ void unpack_bits_gather_kernel(const unsigned char *__restrict__ packed, const int *__restrict__ idx, float *__restrict__ out,
@@ -338,13 +333,13 @@ __global__ void convert_bf16_fp8_kernel(const bf16x8 *__restrict__ src, u32x2 *_
         if (dtype != VV_F32 && dtype != VV_BF16 && dtype != VV_FP8) return VV_ERR_DTYPE;                       \
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);                                                \
         if (dtype == VV_BF16)                                                                                  \
-            VV_LAUNCH((KERNEL<__bf16>), dim3(grid_for(TOTAL)), dim3(256), 0, st, w_keras,             \
+            VV_LAUNCH((KERNEL<__bf16>), dim3(vv_grid_1d(TOTAL)), dim3(256), 0, st, w_keras,                    \
                                reinterpret_cast<__bf16 *>(packed), __VA_ARGS__);                               \
         else if (dtype == VV_FP8)                                                                              \
-            VV_LAUNCH((KERNEL<vv_fp8>), dim3(grid_for(TOTAL)), dim3(256), 0, st, w_keras,             \
+            VV_LAUNCH((KERNEL<vv_fp8>), dim3(vv_grid_1d(TOTAL)), dim3(256), 0, st, w_keras,                    \
                                reinterpret_cast<vv_fp8 *>(packed), __VA_ARGS__);                               \
         else                                                                                                   \
-            VV_LAUNCH((KERNEL<float>), dim3(grid_for(TOTAL)), dim3(256), 0, st, w_keras,              \
+            VV_LAUNCH((KERNEL<float>), dim3(vv_grid_1d(TOTAL)), dim3(256), 0, st, w_keras,                     \
                                reinterpret_cast<float *>(packed), __VA_ARGS__);                                \
         return vv_launch_status();                                                                             \
     } while (0)
@@ -410,14 +405,14 @@ VV_EXPORT int vv_pack_conv_k4s1_full(const float *w_keras, void *packed, int sid
 VV_EXPORT int vv_sigmoid_f32(const float *x, float *y, long n, void *stream) {
     if (!x || !y) return VV_ERR_NULL;
     if (n <= 0) return VV_ERR_SHAPE;
-    VV_LAUNCH(sigmoid_f32_kernel, dim3(grid_for((size_t)n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, y, n);
+    VV_LAUNCH(sigmoid_f32_kernel, dim3(vv_grid_1d((size_t)n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, y, n);
     return vv_launch_status();
 }
 
 VV_EXPORT int vv_max_over_positions(const float *x, float *out, int batch, int npos, int channels, void *stream) {
     if (!x || !out) return VV_ERR_NULL;
     if (batch <= 0 || npos <= 0 || channels <= 0) return VV_ERR_SHAPE;
-    VV_LAUNCH(max_over_positions_kernel, dim3(grid_for((size_t)batch * channels)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, out,
+    VV_LAUNCH(max_over_positions_kernel, dim3(vv_grid_1d((size_t)batch * channels)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, out,
               batch, npos, channels);
     return vv_launch_status();
 }
@@ -438,7 +433,7 @@ VV_EXPORT int vv_fold_bn(const float *gamma, const float *beta, const float *mea
                          float eps, float *scale, float *shift, int channels, int repeat, void *stream) {
     if (!gamma || !beta || !mean || !var || !scale || !shift) return VV_ERR_NULL;
     if (channels <= 0 || repeat <= 0) return VV_ERR_SHAPE;
-    VV_LAUNCH(fold_bn_kernel, dim3(grid_for((size_t)channels * repeat)), dim3(256), 0,
+    VV_LAUNCH(fold_bn_kernel, dim3(vv_grid_1d((size_t)channels * repeat)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), gamma, beta, mean, var, bias, eps, scale, shift, channels,
                        repeat);
     return vv_launch_status();
@@ -473,7 +468,7 @@ VV_EXPORT int vv_unpack_bits_gather(const void *packed, const int *index, float 
     if (batch <= 0 || voxels <= 0 || voxels % 8) return VV_ERR_SHAPE;
     if (!vv_aligned16(out)) return VV_ERR_ALIGN;
     const long bps = voxels / 8, total = bps * batch;
-    VV_LAUNCH(unpack_bits_gather_kernel, dim3(grid_for((size_t)total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    VV_LAUNCH(unpack_bits_gather_kernel, dim3(vv_grid_1d((size_t)total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
               reinterpret_cast<const unsigned char *>(packed), index, out, bps, total);
     return vv_launch_status();
 }
@@ -482,7 +477,7 @@ VV_EXPORT int vv_pack_bits(const float *x, void *packed, float threshold, long n
     if (!x || !packed) return VV_ERR_NULL;
     if (n <= 0 || n % 8) return VV_ERR_SHAPE;
     if (!vv_aligned16(x)) return VV_ERR_ALIGN;
-    VV_LAUNCH(pack_bits_kernel, dim3(grid_for((size_t)(n / 8))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x,
+    VV_LAUNCH(pack_bits_kernel, dim3(vv_grid_1d((size_t)(n / 8))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x,
               reinterpret_cast<unsigned char *>(packed), threshold, n / 8);
     return vv_launch_status();
 }
@@ -493,9 +488,9 @@ VV_EXPORT int vv_convert(const void *src, void *dst, long n, int src_dtype, int 
     if (dst_dtype != VV_F32 && dst_dtype != VV_BF16 && dst_dtype != VV_FP8) return VV_ERR_DTYPE;
     if (n <= 0) return VV_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 g(grid_for((size_t)n)), b(256);
+    const dim3 g(vv_grid_1d((size_t)n)), b(256);
     if (src_dtype == VV_BF16 && dst_dtype == VV_FP8 && n % 8 == 0 && vv_aligned16(src) && vv_aligned16(dst))
-        VV_LAUNCH(convert_bf16_fp8_kernel, dim3(grid_for((size_t)(n / 8))), b, 0, st, reinterpret_cast<const bf16x8 *>(src), reinterpret_cast<u32x2 *>(dst), n / 8);
+        VV_LAUNCH(convert_bf16_fp8_kernel, dim3(vv_grid_1d((size_t)(n / 8))), b, 0, st, reinterpret_cast<const bf16x8 *>(src), reinterpret_cast<u32x2 *>(dst), n / 8);
     else if (dst_dtype == VV_FP8 && src_dtype == VV_F32)
         VV_LAUNCH((convert_kernel<float, vv_fp8>), g, b, 0, st, reinterpret_cast<const float *>(src), reinterpret_cast<vv_fp8 *>(dst), n);
     else if (dst_dtype == VV_FP8 && src_dtype == VV_BF16)

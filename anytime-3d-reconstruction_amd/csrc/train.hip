@@ -2,8 +2,6 @@
 // activation backward, weight gradients as reduction-over-rows GEMMs on the exact-f32 MFMA, BCE / reparameterisation
 // backward, Adam.  Data gradients reuse the forward implicit-GEMM kernels (the data gradient of a stride-2 conv IS the
 // transposed conv with the same Keras kernel array, and vice versa).  float32 only this round.  gfx950.
-#include <stdlib.h>
-
 #include "common.h"
 
 namespace {
@@ -540,7 +538,7 @@ __global__ __launch_bounds__(256, ONE ? 4 : 2) void wgrad_bf16_kernel(const Wgra
         stage(rc, 0);
     }
     for (; rc < r_end; rc += BR, st ^= 1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vv_wait_vm<0>();
         __syncthreads();                                     // chunk landed for everyone; previous chunk's reads are done
         const bool more = rc + BR < r_end;
         if (more) {
@@ -865,11 +863,6 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T *__restrict__ x, fl
     }
 }
 
-inline int grid_1d(long n) {
-    long g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
-}
-
 // Row blocks of the two BatchNorm sweeps: 256 rows per block on the long layers (at most 1024 blocks), but never fewer
 // blocks than keep ~16 rows per block -- a 2048-row x 512-channel layer is 128 blocks, not 8.
 // A thread owns V consecutive channels (4 floats / 8 bf16) and a workgroup spans whole rows: C % V == 0, C / V <= 256
@@ -885,7 +878,7 @@ inline int bn_sweep_blocks(long R, int C, int V) {
     const int cvn = C / V;
     const int rows_par = 256 / cvn > 0 ? 256 / cvn : 1;
     long nb = (R + 2L * rows_par - 1) / (2L * rows_par);
-    static const long cap = vv_hook("VV_BN_SWEEP") ? atol(vv_hook("VV_BN_SWEEP")) : 4096;
+    static const long cap = vv_hook_int(vv_hook("VV_BN_SWEEP"), 4096);
     return (int)(nb > cap ? cap : (nb < 1 ? 1 : nb));
 }
 
@@ -896,7 +889,7 @@ inline int bn_blocks(long R, int C, int V = 4) {
     if (per < 16) per = 16;
     if (per > 256) per = 256;
     long nb = (R + per - 1) / per;
-    static const long cap = vv_hook("VV_BN_NB") ? atol(vv_hook("VV_BN_NB")) : 1024;
+    static const long cap = vv_hook_int(vv_hook("VV_BN_NB"), 1024);
     return (int)(nb > cap ? cap : (nb < 1 ? 1 : nb));
 }
 
@@ -1028,7 +1021,7 @@ void launch_wgrad_reduce(const float *slabs, float *out, long n, int splits, flo
     if (splits >= 16 && n <= 65536)
         VV_LAUNCH(wgrad_reduce_sliced_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, slabs, out, n, splits, alpha, accumulate);
     else
-        VV_LAUNCH(wgrad_reduce_kernel, dim3(grid_1d(n)), dim3(256), 0, st, slabs, out, n, splits, alpha, accumulate);
+        VV_LAUNCH(wgrad_reduce_kernel, dim3(vv_grid_1d(n, 16384)), dim3(256), 0, st, slabs, out, n, splits, alpha, accumulate);
 }
 
 template <int AMODE>
@@ -1046,11 +1039,7 @@ int launch_wgrad_bf16(const WgradBArgs &a_in, const WgradPlan &p, float *out, hi
     WgradBArgs a = a_in;
     if (p.splits == 1) a.slabs = out;              // one share: its "slab" IS the result (the reduce pass was a 33 MB copy on the 256 <-> 512 layers)
     const int tiles = ((a.M + 127) / 128) * ((a.N + 127) / 128);
-    static const bool attr = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_bf16_kernel<AMODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-        return true;
-    }();
-    (void)attr;
+    vv_allow_lds<&wgrad_bf16_kernel<AMODE>>(65536);
     if (AMODE == 2 && a.N <= 64) VV_LAUNCH((wgrad_bf16_kernel<2, true>), dim3(tiles, p.splits), dim3(256), 32768, st, a);
     else VV_LAUNCH((wgrad_bf16_kernel<AMODE>), dim3(tiles, p.splits), dim3(256), 65536, st, a);
     const long n = (long)a.M * a.N;
@@ -1129,7 +1118,7 @@ VV_EXPORT int vv_unpack_meanpool_grad(const float *dpanel, float *dw, int side, 
                   side, cin, cout);
         return vv_launch_status();
     }
-    VV_LAUNCH(unpack_meanpool_grad_kernel, dim3(grid_1d((long)64 * cin * cout)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    VV_LAUNCH(unpack_meanpool_grad_kernel, dim3(vv_grid_1d((long)64 * cin * cout, 16384)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
               dpanel, dw, side, cin, cout);
     return vv_launch_status();
 }
@@ -1137,7 +1126,7 @@ VV_EXPORT int vv_unpack_meanpool_grad(const float *dpanel, float *dw, int side, 
 VV_EXPORT int vv_unpack_convT_dense_grad(const float *dpanel, float *dw, int side, int cin, int cout, void *stream) {
     if (!dpanel || !dw) return VV_ERR_NULL;
     if (side <= 0 || cin <= 0 || cout <= 0) return VV_ERR_SHAPE;
-    VV_LAUNCH(unpack_convT_dense_grad_kernel, dim3(grid_1d((long)64 * cin * cout)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    VV_LAUNCH(unpack_convT_dense_grad_kernel, dim3(vv_grid_1d((long)64 * cin * cout, 16384)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
               dpanel, dw, side, cin, cout);
     return vv_launch_status();
 }
@@ -1154,7 +1143,7 @@ VV_EXPORT int vv_bce_bwd(const float *probs, const float *target, float *dlogit,
     if (!probs || !target || !dlogit) return VV_ERR_NULL;
     if (batch <= 0 || voxels <= 0) return VV_ERR_SHAPE;
     const long n = (long)batch * voxels;
-    VV_LAUNCH(bce_bwd_kernel, dim3(grid_1d(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), probs, target, dlogit, n, gamma,
+    VV_LAUNCH(bce_bwd_kernel, dim3(vv_grid_1d(n, 16384)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), probs, target, dlogit, n, gamma,
               epsilon, inv_batch);
     return vv_launch_status();
 }
@@ -1172,7 +1161,7 @@ VV_EXPORT int vv_adam_step(float *param, const float *grad, float *m, float *v, 
                            float epsilon, void *stream) {
     if (!param || !grad || !m || !v) return VV_ERR_NULL;
     if (n <= 0) return VV_ERR_SHAPE;
-    VV_LAUNCH(adam_kernel, dim3(grid_1d(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), param, grad, m, v, n, lr_t, beta1,
+    VV_LAUNCH(adam_kernel, dim3(vv_grid_1d(n, 16384)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), param, grad, m, v, n, lr_t, beta1,
               beta2, epsilon);
     return vv_launch_status();
 }

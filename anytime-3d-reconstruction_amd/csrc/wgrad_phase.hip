@@ -180,7 +180,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_phase_kernel(const WgPhaseArgs a
     if (box0 < box1) stage(box0, 0);
 #pragma unroll 1
     for (int box = box0; box < box1; ++box, st ^= 1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vv_wait_vm<0>();
         __syncthreads();                                   // this box landed for everyone; the previous box's reads are done
         if (box + 1 < box1) stage(box + 1, st ^ 1);
         const unsigned xa = xa0 + st * G::STAGE, ga = ga0 + st * G::STAGE;
@@ -247,11 +247,7 @@ WgPhasePlan wg_phase_plan(long rows, int cin, int cout) {
 template <int LS>
 void wg_phase_launch(const WgPhaseArgs &a, int kinds, hipStream_t st) {
     using G = WgGeo<LS>;
-    static const bool attr = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_phase_kernel<LS>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * G::STAGE);
-        return true;
-    }();
-    (void)attr;
+    vv_allow_lds<&wgrad_phase_kernel<LS>>(2 * G::STAGE);
     VV_LAUNCH((wgrad_phase_kernel<LS>), dim3(kinds * a.splits), dim3(512), 2 * G::STAGE, st, a);
 }
 

@@ -1,12 +1,15 @@
 """A/B of two library builds on the chip-wide MFMA layers at batch 256, back to back and interleaved: D4 (vv_convT3d_k4s2_whole_fwd),
 E2 (vv_conv3d_k4s2_direct_fwd; E2fp8: vv_conv3d_k4s2_direct_fp8_fwd), E3 / D3 (vv_conv3d_k4s2_skip_fwd / vv_convT3d_k4s2_skip_fwd).  Outputs must be bit-identical.
-usage: mb_ab_lib.py <other lib .so> [name]      (the tree's library is 'tree')"""
+E2 runs conv_direct16_kernel; its two other forms are reached only through VV_CD_SHAPE, so E2s32 (conv_direct_kernel) and E2h
+(conv_direct16h_kernel) compare the two builds' HOOKS libraries and run only when the other build's hooks library is given.
+usage: mb_ab_lib.py <other lib .so> [name [other hooks lib .so]]      (the tree's library is 'tree')"""
 import ctypes, json, os, sys, time
 import torch
 _R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, _R); sys.path.insert(0, os.path.join(_R, 'anytime-3d-reconstruction_amd'))
 from voxvae import lib as L
 other = sys.argv[2] if len(sys.argv) > 2 else 'base'
 libs = {other: ctypes.CDLL(os.path.join(_R, sys.argv[1])), 'tree': L.load()}
+hooks_libs = {other: ctypes.CDLL(os.path.join(_R, sys.argv[3])), 'tree': ctypes.CDLL(L.HOOKS_LIB_PATH)} if len(sys.argv) > 3 else None
 DEV = 'cuda:0'; B = 256
 cs = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 torch.manual_seed(0)
@@ -48,12 +51,19 @@ _w2 = (torch.randn(4, 4, 4, 64, 128, device=DEV) / 64).float().contiguous()
 L.call('vv_pack_conv_k4', L.ptr(_w2), L.ptr(w2f), 64, 128, L.VV_FP8, cs)
 x2f = torch.randn(B, 16, 16, 16, 64, device=DEV).to(torch.float8_e4m3fn)
 cases['E2fp8'] = ('vv_conv3d_k4s2_direct_fp8_fwd', lambda y: (L.ptr(x2f), L.ptr(w2f), L.ptr(sc), L.ptr(sh), L.ptr(y), B, 16, 64, 128, 1, L.VV_BF16, cs), (B, 8, 8, 8, 128))
+if hooks_libs:       # (fn, args, output shape, environment of the hooks libraries: read at every call)
+    cases['E2s32'] = cases['E2'] + ({'VV_CD_SHAPE': '32'},)
+    cases['E2h'] = cases['E2'] + ({'VV_CD_SHAPE': '8'},)
 
 only = os.environ.get('AB_ONLY', '').split(',') if os.environ.get('AB_ONLY') else list(cases)
 N = 300
 res = {}
+release_libs = libs
 for name in only:
-    fn, args, oshape = cases[name]
+    fn, args, oshape = cases[name][:3]
+    env = cases[name][3] if len(cases[name]) > 3 else {}
+    libs = hooks_libs if env else release_libs
+    os.environ.update(env)
     ys = {k: torch.empty(*oshape, dtype=torch.bfloat16, device=DEV) for k in libs}
     fs = {}
     for k in libs:
@@ -76,4 +86,6 @@ for name in only:
             t[k].append(1e6 * (time.perf_counter() - t0) / N)
     res[name] = {'bit_identical': same, 'us_per_launch': {k: [round(v, 2) for v in t[k]] for k in libs},
                  'tree_over_%s' % other: round(min(t['tree']) / min(t[other]), 4)}
+    for k in env:
+        del os.environ[k]
     print(json.dumps({name: res[name]}), flush=True)

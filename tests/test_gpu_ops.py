@@ -34,6 +34,9 @@ def _bf16_round(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.bfloat16).to(torch.float32).numpy()
 
 
+_ACT = {0: None, 1: 'elu', 2: 'relu', 3: 'lrelu'}     # VV_ACT_* -> oracle name
+
+
 def _tol(dtname):
     return (2e-5, 1e-5) if dtname == 'f32' else (2e-2, 2e-2)   # (rtol on max|ref|, atol)
 
@@ -50,7 +53,7 @@ def _check(got, ref, dtname, what):
 # B >= 32 switches small grids to position-major rows with padded-tap skipping
 @pytest.mark.parametrize('B,side,cin,cout', [(2, 8, 64, 128), (3, 4, 128, 64), (1, 16, 64, 128), (5, 2, 256, 512),
                                              (32, 4, 128, 64), (37, 8, 64, 128), (64, 2, 64, 64)])
-def test_conv3d_k4s2(L, dtname, B, side, cin, cout):
+def test_conv3d_k4s2(L, dtname, B, side, cin, cout, act=1):
     rng = np.random.default_rng(B * 1000 + side)
     dt, tdt = L.DTYPES[dtname], (torch.float32 if dtname == 'f32' else torch.bfloat16)
     x = rng.standard_normal((B, side, side, side, cin)).astype(np.float32)
@@ -59,7 +62,7 @@ def test_conv3d_k4s2(L, dtname, B, side, cin, cout):
     shift = rng.normal(0, 0.3, cout).astype(np.float32)
     if dtname == 'bf16':
         x, w = _bf16_round(x), _bf16_round(w)
-    ref = no.activation(no.conv3d_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, 'elu')
+    ref = no.activation(no.conv3d_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, _ACT[act])
     xd, wd, scd, shd = _dev(x, tdt), _dev(w), _dev(scale), _dev(shift)
     wp = torch.empty(cout, 64 * cin, dtype=tdt, device=DEV)
     L.call('vv_pack_conv_k4', L.ptr(wd), L.ptr(wp), cin, cout, dt, _st())
@@ -67,7 +70,7 @@ def test_conv3d_k4s2(L, dtname, B, side, cin, cout):
     ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=DEV)
     y = torch.empty(B, side // 2, side // 2, side // 2, cout, dtype=tdt, device=DEV)
     L.call('vv_conv3d_k4s2_fwd', L.ptr(xd), L.ptr(wp), L.ptr(scd), L.ptr(shd), L.ptr(y), B, side, cin, cout,
-           1, dt, L.ptr(ws), ws.numel(), _st())
+           act, dt, L.ptr(ws), ws.numel(), _st())
     torch.cuda.synchronize()
     _check(y, ref, dtname, 'conv3d_k4s2')
 
@@ -75,7 +78,7 @@ def test_conv3d_k4s2(L, dtname, B, side, cin, cout):
 @pytest.mark.parametrize('dtname', ['f32', 'bf16'])
 @pytest.mark.parametrize('B,side,cin,cout', [(2, 4, 128, 64), (3, 2, 512, 256), (1, 8, 128, 64), (2, 1, 64, 128),
                                              (33, 2, 64, 128), (40, 4, 64, 64), (64, 1, 64, 64)])
-def test_convT3d_k4s2(L, dtname, B, side, cin, cout):
+def test_convT3d_k4s2(L, dtname, B, side, cin, cout, act=1):
     rng = np.random.default_rng(B * 77 + side)
     dt, tdt = L.DTYPES[dtname], (torch.float32 if dtname == 'f32' else torch.bfloat16)
     x = rng.standard_normal((B, side, side, side, cin)).astype(np.float32)
@@ -84,7 +87,7 @@ def test_convT3d_k4s2(L, dtname, B, side, cin, cout):
     shift = rng.normal(0, 0.3, cout).astype(np.float32)
     if dtname == 'bf16':
         x, w = _bf16_round(x), _bf16_round(w)
-    ref = no.activation(no.conv3d_transpose_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, 'elu')
+    ref = no.activation(no.conv3d_transpose_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, _ACT[act])
     xd, wd, scd, shd = _dev(x, tdt), _dev(w), _dev(scale), _dev(shift)
     wp = torch.empty(8, cout, 8 * cin, dtype=tdt, device=DEV)
     L.call('vv_pack_convT_k4s2', L.ptr(wd), L.ptr(wp), cin, cout, dt, _st())
@@ -92,7 +95,7 @@ def test_convT3d_k4s2(L, dtname, B, side, cin, cout):
     ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=DEV)
     y = torch.empty(B, 2 * side, 2 * side, 2 * side, cout, dtype=tdt, device=DEV)
     L.call('vv_convT3d_k4s2_fwd', L.ptr(xd), L.ptr(wp), L.ptr(scd), L.ptr(shd), L.ptr(y), B, side, cin, cout,
-           1, dt, L.ptr(ws), ws.numel(), _st())
+           act, dt, L.ptr(ws), ws.numel(), _st())
     torch.cuda.synchronize()
     _check(y, ref, dtname, 'convT3d_k4s2')
 
@@ -107,7 +110,7 @@ def test_conv3d_k4s2_skip(L, B, cin, cout, act):
     scale = rng.uniform(0.5, 1.5, cout).astype(np.float32)
     shift = rng.normal(0, 0.3, cout).astype(np.float32)
     assert L.load().vv_conv3d_k4s2_skip_supported(8, cin, cout, L.VV_BF16)
-    ref = no.activation(no.conv3d_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, 'elu' if act else None)
+    ref = no.activation(no.conv3d_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, _ACT[act])
     xd, wd, scd, shd = _dev(x, torch.bfloat16), _dev(w), _dev(scale), _dev(shift)
     wp = torch.empty(64 * cin * cout, dtype=torch.bfloat16, device=DEV)
     L.call('vv_pack_conv_k4_skip', L.ptr(wd), L.ptr(wp), cin, cout, _st())
@@ -126,7 +129,7 @@ def test_convT3d_k4s2_skip(L, B, cin, cout, act):
     scale = rng.uniform(0.5, 1.5, cout).astype(np.float32)
     shift = rng.normal(0, 0.3, cout).astype(np.float32)
     assert L.load().vv_convT3d_k4s2_skip_supported(4, cin, cout, L.VV_BF16)
-    ref = no.activation(no.conv3d_transpose_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, 'elu' if act else None)
+    ref = no.activation(no.conv3d_transpose_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, _ACT[act])
     xd, wd, scd, shd = _dev(x, torch.bfloat16), _dev(w), _dev(scale), _dev(shift)
     wp = torch.empty(64 * cin * cout, dtype=torch.bfloat16, device=DEV)
     L.call('vv_pack_convT_k4s2_skip', L.ptr(wd), L.ptr(wp), cin, cout, _st())
@@ -258,7 +261,7 @@ def test_conv3d_k4s2_pos(L, B, cin, cout, act):
     scale = rng.uniform(0.5, 1.5, cout).astype(np.float32)
     shift = rng.normal(0, 0.3, cout).astype(np.float32)
     assert L.load().vv_conv3d_k4s2_pos_supported(4, cin, cout, L.VV_BF16)
-    ref = no.activation(no.conv3d_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, 'elu' if act else None)
+    ref = no.activation(no.conv3d_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, _ACT[act])
     xd, wd, scd, shd = _dev(x, torch.bfloat16), _dev(w), _dev(scale), _dev(shift)
     wp = torch.empty(64 * cin * cout, dtype=torch.bfloat16, device=DEV)
     L.call('vv_pack_conv_k4_skip', L.ptr(wd), L.ptr(wp), cin, cout, _st())
@@ -279,7 +282,7 @@ def test_convT3d_k4s2_pos(L, B, cin, cout, act):
     scale = rng.uniform(0.5, 1.5, cout).astype(np.float32)
     shift = rng.normal(0, 0.3, cout).astype(np.float32)
     assert L.load().vv_convT3d_k4s2_pos_supported(2, cin, cout, L.VV_BF16)
-    ref = no.activation(no.conv3d_transpose_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, 'elu' if act else None)
+    ref = no.activation(no.conv3d_transpose_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, _ACT[act])
     xd, wd, scd, shd = _dev(x, torch.bfloat16), _dev(w), _dev(scale), _dev(shift)
     wp = torch.empty(64 * cin * cout, dtype=torch.bfloat16, device=DEV)
     L.call('vv_pack_convT_k4s2_skip', L.ptr(wd), L.ptr(wp), cin, cout, _st())
@@ -293,7 +296,7 @@ def test_convT3d_k4s2_pos(L, B, cin, cout, act):
 
 @pytest.mark.parametrize('dtname', ['f32', 'bf16'])
 @pytest.mark.parametrize('M,N,K', [(4, 64, 64), (7, 128, 16), (256, 128, 4096), (130, 4096, 64), (2, 64, 8200)])
-def test_dense(L, dtname, M, N, K):
+def test_dense(L, dtname, M, N, K, act=1):
     rng = np.random.default_rng(M + N + K)
     dt, tdt = L.DTYPES[dtname], (torch.float32 if dtname == 'f32' else torch.bfloat16)
     x = rng.standard_normal((M, K)).astype(np.float32)
@@ -302,14 +305,14 @@ def test_dense(L, dtname, M, N, K):
         x, w = _bf16_round(x), _bf16_round(w)
     scale = rng.uniform(0.5, 1.5, N).astype(np.float32)
     shift = rng.normal(0, 0.3, N).astype(np.float32)
-    ref = no.activation(x.astype(np.float64) @ w.astype(np.float64) * scale + shift, 'elu')
+    ref = no.activation(x.astype(np.float64) @ w.astype(np.float64) * scale + shift, _ACT[act])
     wp = torch.empty(N, K, dtype=tdt, device=DEV)
     wd, xd, scd, shd = _dev(w), _dev(x, tdt), _dev(scale), _dev(shift)
     L.call('vv_pack_dense', L.ptr(wd), L.ptr(wp), K, N, dt, _st())
     nb = L.load().vv_dense_workspace_bytes(M, N, K, dt)
     ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=DEV)
     y = torch.empty(M, N, dtype=torch.float32, device=DEV)
-    L.call('vv_dense_fwd', L.ptr(xd), L.ptr(wp), L.ptr(scd), L.ptr(shd), L.ptr(y), M, N, K, 1, dt,
+    L.call('vv_dense_fwd', L.ptr(xd), L.ptr(wp), L.ptr(scd), L.ptr(shd), L.ptr(y), M, N, K, act, dt,
            L.VV_F32, L.ptr(ws), ws.numel(), _st())
     torch.cuda.synchronize()
     _check(y, ref, 'f32' if dtname == 'f32' else 'bf16', 'dense')
@@ -318,7 +321,7 @@ def test_dense(L, dtname, M, N, K):
 @pytest.mark.parametrize('dtname', ['f32', 'bf16'])
 # D >= 32 (bf16) takes the plane-form kernel, smaller grids the gather form; B = 7 leaves a ragged last workgroup
 @pytest.mark.parametrize('B,D', [(2, 32), (1, 16), (3, 8), (7, 32), (1, 64), (1, 128)])
-def test_conv3d_first(L, dtname, B, D):
+def test_conv3d_first(L, dtname, B, D, act=1):
     from voxvae import synthetic as syn
     rng = np.random.default_rng(D)
     dt, tdt = L.DTYPES[dtname], (torch.float32 if dtname == 'f32' else torch.bfloat16)
@@ -326,13 +329,13 @@ def test_conv3d_first(L, dtname, B, D):
     w = (rng.standard_normal((4, 4, 4, 1, 64)) / 8).astype(np.float32)
     scale = rng.uniform(0.5, 1.5, 64).astype(np.float32)
     shift = rng.normal(0, 0.3, 64).astype(np.float32)
-    ref = no.activation(no.conv3d_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, 'elu')
+    ref = no.activation(no.conv3d_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, _ACT[act])
     y = torch.empty(B, D // 2, D // 2, D // 2, 64, dtype=tdt, device=DEV)
     xd, wd, scd, shd = _dev(x), _dev(w), _dev(scale), _dev(shift)
     wp = torch.empty(64, 64, dtype=tdt, device=DEV)
     L.call('vv_pack_conv_k4', L.ptr(wd), L.ptr(wp), 1, 64, dt, _st())
     L.call('vv_conv3d_first_fwd', L.ptr(xd), L.ptr(wp), L.ptr(scd), L.ptr(shd), L.ptr(y), B, D, 64,
-           1, dt, _st())
+           act, dt, _st())
     torch.cuda.synchronize()
     rt = 'f32' if dtname == 'f32' else 'bf16'
     got = y.float().cpu().numpy()
@@ -407,7 +410,7 @@ def test_convT3d_final_bce(L, dtname, B, side, form, monkeypatch):
 
 @pytest.mark.parametrize('B,K5,Lz,lin,n1,variational', [(256, 4096, 64, 64, 4096, True), (37, 4096, 64, 64, 4096, False),
                                                         (5, 1024, 32, 512, 2048, True), (19, 8200, 64, 96, 80, True)])
-def test_latent_tail(L, B, K5, Lz, lin, n1, variational):
+def test_latent_tail(L, B, K5, Lz, lin, n1, variational, act=1):
     """encoder tail -> clip | sampling | KL -> Dense + BN + act -> first decoder layer (dense panel) + BN + act in two launches
     (latent_tail.hip) against the float64 definition on the same bf16 operands."""
     rng = np.random.default_rng(B + K5)
@@ -439,7 +442,7 @@ def test_latent_tail(L, B, K5, Lz, lin, n1, variational):
     ws = torch.empty(max(L.load().vv_latent_tail_workspace_bytes(B, K5, E, n1), 16), dtype=torch.uint8, device=DEV)
     L.call('vv_latent_tail_fwd', L.ptr(hd), L.ptr(w5d), None, L.ptr(epsd) if variational else None, L.ptr(wdd), L.ptr(scdd), L.ptr(shdd),
            L.ptr(w1d), L.ptr(sc1d), L.ptr(sh1d), L.ptr(enc_out), L.ptr(z), L.ptr(zb), L.ptr(kl) if variational else None, L.ptr(h1),
-           B, K5, E, Lz, lin, n1, int(variational), 1, L.VV_BF16, L.ptr(ws), ws.numel(), _st())
+           B, K5, E, Lz, lin, n1, int(variational), act, L.VV_BF16, L.ptr(ws), ws.numel(), _st())
     torch.cuda.synchronize()
     np.testing.assert_allclose(enc_out.cpu().numpy(), enc, rtol=0, atol=2e-5 * max(1.0, np.abs(enc).max()))
     np.testing.assert_allclose(z.cpu().numpy(), zr, rtol=2e-5, atol=2e-5 * max(1.0, np.abs(zr).max()))
@@ -448,9 +451,9 @@ def test_latent_tail(L, B, K5, Lz, lin, n1, variational):
     assert torch.equal(zb, z.to(bt))
     # the two dense layers on the kernel's own bf16 latent (what the split path feeds them too)
     zq = zb.float().cpu().numpy().astype(np.float64)
-    t = no.activation(zq @ wd.astype(np.float64).T * scd + shd, 'elu')
+    t = no.activation(zq @ wd.astype(np.float64).T * scd + shd, _ACT[act])
     tq = _bf16_round(t.astype(np.float32)).astype(np.float64)
-    ref = no.activation(tq @ w1.astype(np.float64).T * sc1 + sh1, 'elu')
+    ref = no.activation(tq @ w1.astype(np.float64).T * sc1 + sh1, _ACT[act])
     _check(h1, ref, 'bf16', 'latent_tail')
 
 
@@ -460,7 +463,7 @@ def test_latent_tail(L, B, K5, Lz, lin, n1, variational):
 # itself, against the float64 definition through the encoder output.
 @pytest.mark.parametrize('B,cin,cout,Lz,variational', [(256, 256, 512, 64, True), (37, 64, 256, 32, True), (300, 128, 512, 64, False),
                                                        (5, 64, 256, 64, True)])
-def test_conv_pos_latent_tail_fused(L, B, cin, cout, Lz, variational):
+def test_conv_pos_latent_tail_fused(L, B, cin, cout, Lz, variational, act=1):
     rng = np.random.default_rng(B * 7 + cin)
     E = 2 * Lz if variational else Lz
     K5, lin, n1 = 8 * cout, 64, 4096
@@ -490,12 +493,12 @@ def test_conv_pos_latent_tail_fused(L, B, cin, cout, Lz, variational):
     # the two calls
     ws = torch.empty(max(lib.vv_conv3d_k4s2_pos_workspace_bytes(B, cin, cout), 16), dtype=torch.uint8, device=DEV)
     h4 = torch.full((B, 2, 2, 2, cout), float('nan'), dtype=bt, device=DEV)
-    L.call('vv_conv3d_k4s2_pos_fwd', L.ptr(xd), L.ptr(wp), L.ptr(sc4d), L.ptr(sh4d), L.ptr(h4), B, 4, cin, cout, 1, L.VV_BF16, L.ptr(ws), ws.numel(), _st())
+    L.call('vv_conv3d_k4s2_pos_fwd', L.ptr(xd), L.ptr(wp), L.ptr(sc4d), L.ptr(sh4d), L.ptr(h4), B, 4, cin, cout, act, L.VV_BF16, L.ptr(ws), ws.numel(), _st())
     e0, z0, zb0, kl0, h10 = outs()
     ws2 = torch.empty(max(lib.vv_latent_tail_workspace_bytes(B, K5, E, n1), 16), dtype=torch.uint8, device=DEV)
     L.call('vv_latent_tail_fwd', L.ptr(h4), L.ptr(w5d), None, L.ptr(epsd) if variational else None, L.ptr(wdd), L.ptr(scdd), L.ptr(shdd),
            L.ptr(w1d), L.ptr(sc1d), L.ptr(sh1d), L.ptr(e0), L.ptr(z0), L.ptr(zb0), L.ptr(kl0) if variational else None, L.ptr(h10),
-           B, K5, E, Lz, lin, n1, int(variational), 1, L.VV_BF16, L.ptr(ws2), ws2.numel(), _st())
+           B, K5, E, Lz, lin, n1, int(variational), act, L.VV_BF16, L.ptr(ws2), ws2.numel(), _st())
     # the fused call
     e1, z1, zb1, kl1, h11 = outs()
     need = lib.vv_conv_pos_latent_tail_workspace_bytes(B, cin, cout, E)
@@ -503,7 +506,7 @@ def test_conv_pos_latent_tail_fused(L, B, cin, cout, Lz, variational):
     ws3 = torch.empty(need, dtype=torch.uint8, device=DEV)
     L.call('vv_conv_pos_latent_tail_fwd', L.ptr(xd), L.ptr(wp), L.ptr(sc4d), L.ptr(sh4d), cin, cout, L.ptr(w5d), None,
            L.ptr(epsd) if variational else None, L.ptr(wdd), L.ptr(scdd), L.ptr(shdd), L.ptr(w1d), L.ptr(sc1d), L.ptr(sh1d), L.ptr(e1), L.ptr(z1),
-           L.ptr(zb1), L.ptr(kl1) if variational else None, L.ptr(h11), B, E, Lz, lin, n1, int(variational), 1, L.VV_BF16, L.ptr(ws3), ws3.numel(), _st())
+           L.ptr(zb1), L.ptr(kl1) if variational else None, L.ptr(h11), B, E, Lz, lin, n1, int(variational), act, L.VV_BF16, L.ptr(ws3), ws3.numel(), _st())
     torch.cuda.synchronize()
     en0, en1 = e0.cpu().numpy().astype(np.float64), e1.cpu().numpy().astype(np.float64)
     tol = 2e-5 * max(1.0, np.abs(en0).max())
@@ -520,7 +523,7 @@ def test_conv_pos_latent_tail_fused(L, B, cin, cout, Lz, variational):
     # too small a workspace is refused, nothing is launched
     assert lib.vv_conv_pos_latent_tail_fwd(L.ptr(xd), L.ptr(wp), L.ptr(sc4d), L.ptr(sh4d), cin, cout, L.ptr(w5d), None, L.ptr(epsd), L.ptr(wdd),
                                            L.ptr(scdd), L.ptr(shdd), L.ptr(w1d), L.ptr(sc1d), L.ptr(sh1d), L.ptr(e1), L.ptr(z1), L.ptr(zb1), L.ptr(kl1),
-                                           L.ptr(h11), B, E, Lz, lin, n1, int(variational), 1, L.VV_BF16, L.ptr(ws3), need - 16, _st()) == -5
+                                           L.ptr(h11), B, E, Lz, lin, n1, int(variational), act, L.VV_BF16, L.ptr(ws3), need - 16, _st()) == -5
 
 
 def test_reparam_kl(L):
@@ -563,7 +566,7 @@ def test_error_codes(L):
 
 @pytest.mark.parametrize('variant', ['8', '4', '2'])
 @pytest.mark.parametrize('B,side', [(2, 8), (1, 16), (3, 8)])
-def test_convT3d_k4s2_direct(L, B, side, variant, monkeypatch):
+def test_convT3d_k4s2_direct(L, B, side, variant, monkeypatch, act=1):
     """LDS-resident input-tile variant of the widest decoder layer (bf16, 128 -> 64): 8 waves x 1 parity (default), and the
     two 4-wave x 2-parity forms."""
     monkeypatch.setenv('VV_DIRECT_MT', variant)
@@ -575,18 +578,18 @@ def test_convT3d_k4s2_direct(L, B, side, variant, monkeypatch):
     w = _bf16_round((rng.standard_normal((4, 4, 4, cout, cin)) / np.sqrt(8 * cin)).astype(np.float32))
     scale = rng.uniform(0.5, 1.5, cout).astype(np.float32)
     shift = rng.normal(0, 0.3, cout).astype(np.float32)
-    ref = no.activation(no.conv3d_transpose_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, 'elu')
+    ref = no.activation(no.conv3d_transpose_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, _ACT[act])
     xd, wd, scd, shd = _dev(x, torch.bfloat16), _dev(w), _dev(scale), _dev(shift)
     wf = torch.empty(64 * cin * cout, dtype=torch.bfloat16, device=DEV)
     L.call('vv_pack_convT_k4s2_frag', L.ptr(wd), L.ptr(wf), cin, cout, _st())
     y = torch.full((B, 2 * side, 2 * side, 2 * side, cout), -7.0, dtype=torch.bfloat16, device=DEV)
-    L.call('vv_convT3d_k4s2_direct_fwd', L.ptr(xd), L.ptr(wf), L.ptr(scd), L.ptr(shd), L.ptr(y), B, side, cin, cout, 1, L.VV_BF16, _st())
+    L.call('vv_convT3d_k4s2_direct_fwd', L.ptr(xd), L.ptr(wf), L.ptr(scd), L.ptr(shd), L.ptr(y), B, side, cin, cout, act, L.VV_BF16, _st())
     torch.cuda.synchronize()
     _check(y, ref, 'bf16', 'convT3d_k4s2_direct')
 
 
 @pytest.mark.parametrize('shape', [16, 32, 8])         # MFMA shape: 16x16x32 (default) / 32x32x16 / 8 = 16x16x32 as two 4-wave workgroups per CU
-@pytest.mark.parametrize('B,side,act', [(2, 16, 1), (1, 32, 1), (3, 16, 0), (5, 16, 2)])
+@pytest.mark.parametrize('B,side,act', [(2, 16, 1), (1, 32, 1), (3, 16, 0), (5, 16, 2), (1, 16, 3)])
 def test_conv3d_k4s2_direct(L, B, side, act, shape, monkeypatch):
     monkeypatch.setenv('VV_CD_SHAPE', str(shape))
     """LDS-resident phase-tile variant of the widest encoder layer (bf16, 64 -> 128); also bit-compared with the
@@ -600,7 +603,7 @@ def test_conv3d_k4s2_direct(L, B, side, act, shape, monkeypatch):
     w = _bf16_round((rng.standard_normal((4, 4, 4, cin, cout)) / np.sqrt(64 * cin)).astype(np.float32))
     scale = rng.uniform(0.5, 1.5, cout).astype(np.float32)
     shift = rng.normal(0, 0.3, cout).astype(np.float32)
-    actname = {0: 'none', 1: 'elu', 2: 'relu'}[act]
+    actname = {0: 'none', 1: 'elu', 2: 'relu', 3: 'lrelu'}[act]
     ref = no.activation(no.conv3d_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, actname)
     xd, wd, scd, shd = _dev(x, torch.bfloat16), _dev(w), _dev(scale), _dev(shift)
     wp = torch.empty(cout, 64 * cin, dtype=torch.bfloat16, device=DEV)
@@ -618,6 +621,31 @@ def test_conv3d_k4s2_direct(L, B, side, act, shape, monkeypatch):
     torch.cuda.synchronize()
     d = (y.float() - y2.float()).abs().max().item()
     assert d <= 2e-2, 'direct vs implicit-GEMM: %.3e' % d
+
+
+# Activation code 3 (LeakyReLU) through every entry point that turns the run-time code into a compile-time constant and whose own
+# parametrisation above stops at ELU / ReLU / none: the test's body at its smallest shape (for the implicit GEMM: the smallest that
+# takes the split-K epilogue, where the constant is chosen).  The direct family and vv_convT3d_k4s2_whole_fwd carry code 3 in their
+# own case lists.  First layer: the plane form against the oracle here (D = 32 is the smallest grid it takes); the chained form is
+# held bit for bit to the plane form at code 3 by test_conv3d_first_chained_equals_plane_form.
+_LRELU_CASES = {
+    'conv3d_first': lambda L, mp: test_conv3d_first(L, 'bf16', 2, 32, act=3),
+    'conv3d_k4s2': lambda L, mp: test_conv3d_k4s2(L, 'bf16', 5, 2, 256, 512, act=3),
+    'convT3d_k4s2': lambda L, mp: test_convT3d_k4s2(L, 'bf16', 2, 1, 64, 128, act=3),
+    'dense': lambda L, mp: test_dense(L, 'bf16', 2, 64, 8200, act=3),
+    'conv3d_k4s2_skip': lambda L, mp: test_conv3d_k4s2_skip(L, 5, 64, 64, 3),
+    'convT3d_k4s2_skip': lambda L, mp: test_convT3d_k4s2_skip(L, 3, 64, 128, 3),
+    'conv3d_k4s2_pos': lambda L, mp: test_conv3d_k4s2_pos(L, 5, 64, 64, 3),
+    'convT3d_k4s2_pos': lambda L, mp: test_convT3d_k4s2_pos(L, 3, 64, 64, 3),
+    'latent_tail': lambda L, mp: test_latent_tail(L, 5, 1024, 32, 512, 2048, True, act=3),
+    'conv_pos_latent_tail_fused': lambda L, mp: test_conv_pos_latent_tail_fused(L, 5, 64, 256, 64, True, act=3),
+    'convT3d_k4s2_direct': lambda L, mp: test_convT3d_k4s2_direct(L, 2, 8, '8', mp, act=3),
+}
+
+
+@pytest.mark.parametrize('entry', sorted(_LRELU_CASES))
+def test_lrelu_through_every_act_dispatch(L, entry, monkeypatch):
+    _LRELU_CASES[entry](L, monkeypatch)
 
 
 def _wgrad_conv_ref(src, g):
@@ -1158,7 +1186,7 @@ def test_conv3d_first_chained_equals_plane_form(L, monkeypatch, out, B, D, act):
 
 
 @pytest.mark.skipif(F8 is None, reason='torch.float8_e4m3fn not available')
-@pytest.mark.parametrize('B,side,act', [(1, 8, 1), (3, 8, 0), (2, 16, 1), (1, 32, 2)])
+@pytest.mark.parametrize('B,side,act', [(1, 8, 1), (3, 8, 0), (2, 16, 1), (1, 32, 2), (1, 8, 3)])
 def test_convT3d_direct_fp8(L, B, side, act):
     """fp8 twin of the direct 128 -> 64 transposed layer (LDS-resident halo tile, K = 64 block-scaled MFMA, bf16 output)
     against the float64 definition on the same fp8-representable operands, and against the fp8 implicit GEMM."""
@@ -1170,7 +1198,7 @@ def test_convT3d_direct_fp8(L, B, side, act):
     w = _fp8_round(rng.standard_normal((4, 4, 4, cout, cin)))
     scale = (rng.uniform(0.5, 1.5, cout) / np.sqrt(8 * cin)).astype(np.float32)
     shift = rng.normal(0, 0.3, cout).astype(np.float32)
-    actname = {0: 'none', 1: 'elu', 2: 'relu'}[act]
+    actname = {0: 'none', 1: 'elu', 2: 'relu', 3: 'lrelu'}[act]
     ref = no.activation(no.conv3d_transpose_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, actname)
     xd, wd, sd, hd = _dev(x).to(F8), _dev(w), _dev(scale), _dev(shift)
     wf = torch.empty(64 * cin * cout, dtype=torch.uint8, device=DEV)
@@ -1195,7 +1223,7 @@ def test_convT3d_direct_fp8(L, B, side, act):
 
 
 @pytest.mark.skipif(F8 is None, reason='torch.float8_e4m3fn not available')
-@pytest.mark.parametrize('B,side,act,odt', [(1, 16, 1, 'bf16'), (3, 16, 0, 'fp8'), (2, 32, 1, 'fp8'), (1, 64, 2, 'bf16')])
+@pytest.mark.parametrize('B,side,act,odt', [(1, 16, 1, 'bf16'), (3, 16, 0, 'fp8'), (2, 32, 1, 'fp8'), (1, 64, 2, 'bf16'), (1, 16, 3, 'bf16')])
 def test_conv3d_direct_fp8(L, B, side, act, odt):
     """fp8 twin of the direct 64 -> 128 layer (phase tiles with 64-byte rows, tap pairs per chunk, K = 64 block-scaled MFMA)
     against the float64 definition on fp8-representable operands, and against the fp8 implicit GEMM (tap-pair rows)."""
@@ -1207,7 +1235,7 @@ def test_conv3d_direct_fp8(L, B, side, act, odt):
     w = _fp8_round(rng.standard_normal((4, 4, 4, cin, cout)))
     scale = (rng.uniform(0.5, 1.5, cout) / np.sqrt(64 * cin)).astype(np.float32)
     shift = rng.normal(0, 0.3, cout).astype(np.float32)
-    actname = {0: 'none', 1: 'elu', 2: 'relu'}[act]
+    actname = {0: 'none', 1: 'elu', 2: 'relu', 3: 'lrelu'}[act]
     ref = no.activation(no.conv3d_same(x.astype(np.float64), w.astype(np.float64), 2) * scale + shift, actname)
     xd, sd, hd = _dev(x).to(F8), _dev(scale), _dev(shift)
     wp = torch.empty(cout, 64 * cin, dtype=F8, device=DEV)
