@@ -51,10 +51,17 @@ def parse(description, train=False, extra=None):
     ap.add_argument('--packed-data', action='store_true', help='host loader that keeps the split as bits and serves PackedVoxels batches (1 bit per voxel over PCIe)')
     ap.add_argument('--pipeline', type=int, default=1, help='test_modelnet_VAE.py: batches in flight (voxvae.streams.HostPipeline); 1 = the reference\'s synchronous loop')
     ap.add_argument('--dump-dir', default=None, help='test_modelnet_VAE.py: save <missing_pr>_cl_label/_gt/_pred.npy here (reference :159-165)')
+    ap.add_argument('--points-dir', default=None, help='test_modelnet_VAE.py: save every batch\'s predictions as point clouds here (batch_<n>_points.npy [N,3], batch_<n>_offsets.npy [B+1]; voxvae.points); needs --pipeline 1')
     ap.add_argument('--sampling', type=int, default=0, help='test_modelnet_VAE.py: also score the sampled-mean reconstruction over this many latents per object (0 = off); needs --pipeline 1.  test_modelnet_PR.py: also accumulate that reconstruction\'s curve')
     if extra is not None:
         extra(ap)
     a = ap.parse_args()
+    if a.points_dir and extra is None:
+        if os.path.basename(sys.argv[0]) != SAMPLING_SCRIPT:
+            ap.error('--points-dir is an option of %s' % SAMPLING_SCRIPT)
+        if a.pipeline > 1:
+            ap.error('--points-dir writes every batch synchronously: use --pipeline 1')
+        save_point_clouds(a.points_dir)
     if a.sampling and extra is None:
         # one script owns the option: elsewhere (train + test getEval in one loop, other model classes) its numbers would mean something else
         if os.path.basename(sys.argv[0]) != SAMPLING_SCRIPT:
@@ -94,6 +101,31 @@ def score_sampled_mean(k):
 
     base.getEval = getEval
 
+
+
+# --points-dir D of test_modelnet_VAE.py, served from here for the same reason as --sampling: every getEval of the model classes is
+# followed by voxvae.points.voxel_points on its prediction (the cells with p > 0.5 in row-major order, largest extent scaled to 1,
+# centred: ModelNet carries no size or pose), made on the device and saved as D/batch_<n>_points.npy [N,3] and D/batch_<n>_offsets.npy
+# [B+1] (object b = rows offsets[b] .. offsets[b+1] - 1), n counting the calls from 0.  getEval's own result is returned untouched;
+# without --points-dir nothing is installed.
+def save_point_clouds(points_dir):
+    import src.module.nolbo as nolbo
+    from voxvae.points import voxel_points
+    base = nolbo._ModelnetBase
+    single = base.getEval
+    state = {'n': 0}
+
+    def getEval(self, inputs, *args, **kw):
+        out = single(self, inputs, *args, **kw)
+        os.makedirs(points_dir, exist_ok=True)
+        cloud = voxel_points(out[0], np.ones((len(out[0]), 3), dtype=np.float32))
+        stem = os.path.join(points_dir, 'batch_%05d' % state['n'])
+        np.save(stem + '_points.npy', cloud.points.cpu().numpy())
+        np.save(stem + '_offsets.npy', cloud.offsets.cpu().numpy())
+        state['n'] += 1
+        return out
+
+    base.getEval = getEval
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Shared loop plumbing of the train_* / test_* entry points.  The reference scripts each carry their own copy of the

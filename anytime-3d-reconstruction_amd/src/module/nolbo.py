@@ -410,6 +410,15 @@ class _ModelnetBase(object):
         mean, logvar = self._posterior(x)
         return self.getSampledShape(mean, logvar, sampling_num, y, _eps=_eps)
 
+    def getSampledPoints(self, mean, logvar, dims, pose=None, sampling_num=32, prob=0.5, surface_only=False, *, _eps=None):
+        """getSampledShape followed by voxvae.points.voxel_points on the averaged prediction: the reference's nolbo_test.getPred ->
+        visualizer.getObjectInRealWorld (objRescaleTransform, visualizer.py:171-188) at latent level, without the probabilities
+        leaving the device.  dims [B,3] = (h, w, l) per object, pose None / [4,4] / [B,4,4].  Returns a voxvae.points.PointCloud
+        (`.split()` is the reference's list of [n_b,3] arrays); the count's 8-byte total is the one thing read back."""
+        from voxvae.points import voxel_points
+        pred = self.getSampledShape(mean, logvar, sampling_num, _eps=_eps)
+        return voxel_points(pred, dims, pose, prob=prob, surface_only=surface_only)
+
     # ---------------------------------------------------------------- precision / recall curves (an extension)
     def getPRCurve(self, inputs, curve, category_vectors=None, missing_prob=0.0, sampling_num=0, corrected=None, *, group=None,
                    training=False, _eps=None, _mask=None, _eps2=None):

@@ -92,6 +92,9 @@ SIGNATURES = {
     'vv_convT3d_final_mean_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _sz, _vp]),
     'vv_pr_curve_workspace_bytes': (_sz, [_i, _l, _i]),
     'vv_pr_curve_accumulate': (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _i, _l, _vp]),
+    'vv_voxel_points_workspace_bytes': (_sz, [_i, _i]),
+    'vv_voxel_points_count': (_i, [_vp, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'vv_voxel_points_emit': (_i, [_vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _sz, _i, _i, _vp]),
     'vv_latent_mask_fill':(_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     'vv_nearest_category': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     'vv_latent_correct': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

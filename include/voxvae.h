@@ -348,6 +348,34 @@ int vv_pr_curve_accumulate(const float *pred, const void *target, int target_pac
                            int batch, long voxels, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Occupancy grids -> posed point clouds (voxel_points.hip): objRescaleTransform of src/visualizer/visualizer.py:171-188 for a batch, on
+ * the device.  Per object b with grid side D: the occupied cells (i, j, k) in increasing flat index v = (i D + j) D + k (numpy's
+ * `offset[mask]` order), lo / hi = their per-axis minimum / maximum, ext = hi - lo, E = max(ext), scale = max(h, w, l) / E (0 when
+ * E == 0), q = (cell - lo) scale - (ext scale) / 2 per axis, point = P[:3,:3] q + P[:3,3] in float32.
+ *   occ           packed == 0: float32 [batch][D^3], at any 4-byte address; a cell is occupied iff p > prob with an ordered compare (a NaN cell is
+ *                 not occupied).  packed != 0: bits, cell v = bit v & 7 of byte v >> 3 of a row of D^3 / 8 bytes
+ *                 (the layout of vv_pack_bits; D^3 % 8 != 0: VV_ERR_SHAPE), `prob` is ignored.
+ *   surface_only  != 0: only occupied cells on the grid boundary or with an unoccupied face neighbour are counted and emitted; bbox (and
+ *                 so the scale) is that of ALL occupied cells either way, so the result is the ordered subset of the full one.
+ *   side          1 .. 128, any value.
+ *   counts        int32 [batch]: cells emitted per object.   bbox int32 [batch][6] = (lo_i, lo_j, lo_k, hi_i, hi_j, hi_k); an object
+ *                 without an occupied cell has (D, D, D, -1, -1, -1) and emits nothing.
+ *   offsets       int64 [batch + 1]: exclusive prefix of counts; offsets[batch] is the total.
+ *   dims          float32 [batch][3] = (h, w, l);  pose float32 [batch][16], row-major 4x4 of which rows 0 .. 2 are used, or NULL (identity).
+ *   points        float32 [capacity][3]: object b's points at rows offsets[b] .. offsets[b + 1] - 1, in cell order (no sort: a cell's row
+ *                 is offsets[b] + the count of its object's earlier 4096-cell pieces + its rank inside its piece).  Rows >= capacity
+ *                 are not written: nothing past capacity * 3 floats is touched and offsets[batch] > capacity tells the caller.
+ * vv_voxel_points_count fills counts / bbox / offsets and the workspace (per-piece counts, prefixes and boxes); vv_voxel_points_emit
+ * needs that workspace and the same occ / packed / prob / surface_only / batch / side.  Integer arithmetic and plain stores only: a given
+ * input gives the same bits on every run.  Pointers need the alignment of their element type and no more. */
+size_t vv_voxel_points_workspace_bytes(int batch, int side);
+int vv_voxel_points_count(const void *occ, int packed, float prob, int surface_only, int batch, int side, int *counts, int *bbox,
+                          long long *offsets, void *workspace, size_t workspace_bytes, void *stream);
+int vv_voxel_points_emit(const void *occ, int packed, float prob, int surface_only, const float *dims, const float *pose,
+                         const long long *offsets, const int *bbox, float *points, long long capacity, const void *workspace,
+                         size_t workspace_bytes, int batch, int side, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Training path (nolboSingleObject_modelnet_category_{VAE,AE}.fit, nolbo.py:1411-1447 / 1230-1258).  float32.
  * Data gradients reuse the forward kernels: d(Conv3D k4 s2)/d(input) = vv_convT3d_k4s2_fwd with the SAME Keras
  * kernel array packed by vv_pack_convT_k4s2 (read as [4,4,4,Cout_T = Cin, Cin_T = Cout]); d(Conv3DTranspose k4 s2)/
