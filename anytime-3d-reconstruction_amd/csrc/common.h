@@ -111,6 +111,10 @@ __device__ __forceinline__ void vv_wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory");
 }
 
+// Byte offset of 16-byte slot `slot` of row `row` in an LDS tile of 128-byte rows (64 bf16), slot-swizzled against bank conflicts of
+// the MFMA operand reads (first_conv.hip, final_bce.hip).
+__device__ __forceinline__ int vv_swz_off(int row, int slot) { return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4); }
+
 // The run-time activation code as a compile-time constant: fn(std::integral_constant<int, VV_ACT_*>{}, further arguments...); an
 // unknown code is VV_ACT_NONE.  This is the one such switch.  Kernels use the macro, so that the four arms are calls in the kernel's
 // own body as if written there: behind a function the inliner, working bottom-up, first merges the four epilogues inside the wrapper
@@ -205,15 +209,21 @@ __device__ __forceinline__ float vv_wave_sum(float v) {
     return v;
 }
 
+// One sample's (bce, TP, FP, FN) sums added to the batch sums of (bce, precision, recall, IoU) (nolbo.py:1498-1501)
+__device__ __forceinline__ void vv_add_shape_metrics(float l, float tp, float fp, float fn, float &bce, float &pr, float &rc, float &iou) {
+    bce += l;
+    pr += tp / (tp + fp + 1e-10f);
+    rc += tp / (tp + fn + 1e-10f);
+    iou += tp / fmaxf(tp + fp + fn, 1.f);
+}
+// small.hip (internal): the launch behind vv_shape_metrics, also the last layer's when its partials are reduced separately
+void vv_shape_metrics_launch(const float *stats, float *out4, int batch, hipStream_t st);
+
 // wgrad_phase.hip (internal): phase-form weight gradient of the stride-2 layers; the caller sums *splits slabs.
 bool vv_wgrad_phase_ok(const void *src, const void *g, int batch, int side, int cin, int cout);
 size_t vv_wgrad_phase_ws(long rows, int cin, int cout);
 void vv_wgrad_phase_launch(const void *src, const void *g, float *slabs, int batch, int side, int cin, int cout, int *splits,
                            hipStream_t st);
-
-// final_bce_fp8.hip (internal): sweep-form last layer with an e4m3fn input; returns the partial blocks per sample.
-int vv_final_bce_sweep_fp8_launch(const void *x, const float *w_keras, const float *target, float *probs, float *logits, float *partials,
-                                  int batch, int side, float gamma, float epsilon, hipStream_t st);
 
 // posgemm.hip (internal): the 4^3 -> 2^3 convolution written as float32 split-K slabs only, in the MFMA FRAGMENT order of the
 // producing workgroup (no transpose on the producer's side).  Piece of (position p, share s, sample tile mt, channel tile nt) =

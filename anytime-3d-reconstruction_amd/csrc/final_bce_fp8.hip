@@ -1,5 +1,5 @@
 // Last transposed conv (64 -> 1) + sigmoid / BCE / TP / FP / FN, sweep form, with the INPUT in fp8 (OCP e4m3fn): the fp8
-// twin of final_bce_sweep_kernel (first_last.hip) for the 'fp8' inference mode, where it halves the largest HBM stream of
+// twin of final_bce_sweep_kernel (final_bce.hip) for the 'fp8' inference mode, where it halves the largest HBM stream of
 // the decoder (the 64-channel activation of the widest layer).  Same decomposition -- one workgroup per 8 x 8 (h, w) cell
 // tile swept through the depth, P_d = X_d W^T on MFMA, scatter-form gather of the 8 taps per output voxel, the four sums
 // in registers -- with
@@ -9,17 +9,20 @@
 //   * the float32 Keras kernel quantised in the kernel prologue, per TAP (the MFMA's output row): w / s_tap -> e4m3fn,
 //     s_tap = max|w[tap]| / 256, and s_tap multiplied back when P is published -- the logits stay float32 sums of
 //     fp8 x fp8 products.
-// Everything after P (gather, hardware exp / log / rcp, threshold on the logit) is the bf16 kernel's code.
-#include "common.h"
+// Shared with the bf16 kernels through final_common.h: geometry constants, tile order, output index and the block reduction.  P is
+// this kernel's own: rows of pitch 36 without a slot key, the tap scales multiplied in at the publish, P_{d-1}[td 2,3] kept in a
+// second PH buffer, and a gather of single dwords from both.  The gather role and the voxel loss (fl_role, fl_pair_stats<FL_HW>
+// in the bf16 P-form sweep) are written out here: as calls they reorder 88 instructions of this kernel, which the fp8 mode times,
+// and that has not been measured.
+#include "final_common.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
-constexpr int F8B_CIN = 64;
-constexpr int SW_ROWS = 100, SW_PP = 36, SW_PSZ = 100 * SW_PP;                 // as in first_last.hip: P row pitch / buffer floats
+constexpr int S8_PP = 36, S8_PSZ = FL_ROWS * S8_PP;                            // P row pitch / buffer floats
 constexpr int S8_XB = 7 * 1024, S8_NX = 2;                                     // X slot: 112 rows x 64 B
-constexpr int S8_LDS = S8_NX * S8_XB + 1024 + 1024 + 3 * SW_PSZ * 4;           // slots, sink, 16 spare rows, P buffers
+constexpr int S8_LDS = S8_NX * S8_XB + 1024 + 1024 + 3 * S8_PSZ * 4;           // slots, sink, 16 spare rows, P buffers
 
 __global__ __launch_bounds__(256, 2) void final_bce_sweep_fp8_kernel(const unsigned char *__restrict__ x, const float *__restrict__ w,
                                                                      const float *__restrict__ target, float *__restrict__ probs,
@@ -28,12 +31,11 @@ __global__ __launch_bounds__(256, 2) void final_bce_sweep_fp8_kernel(const unsig
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *Xs = smem;                                             // ring of 2 planes x [112 rows][64 B], slot-swizzled; 1 KiB sink; 16 spare rows
     float *PL = reinterpret_cast<float *>(smem + S8_NX * S8_XB + 2048);   // P_d[td 0,1]      [100][36]
-    float *PH = PL + SW_PSZ;                                     // P_d / P_{d-1}[td 2,3]  [2][100][33]
+    float *PH = PL + S8_PSZ;                                     // P_d / P_{d-1}[td 2,3]  [2][100][33]
     __shared__ float red[4][4];
     __shared__ float tsc[64];                                    // per-tap weight scales
     const int li = din_log2, n = 1 << li, nt8 = n >> 3, ntile = nt8 * nt8;
-    const int T = gridDim.x;
-    const int wi = (T & 7) ? (int)blockIdx.x : (int)(blockIdx.x & 7) * (T >> 3) + (int)(blockIdx.x >> 3);
+    const int wi = fl_work_item();
     const int tile = wi % ntile, b = wi / ntile;
     const int h0 = (tile / nt8) * 8, w0 = (tile % nt8) * 8;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -52,9 +54,9 @@ __global__ __launch_bounds__(256, 2) void final_bce_sweep_fp8_kernel(const unsig
             const int piece = wv * 2 + i, row = piece * 16 + (lane >> 2);
             const int zh = row / 10, zw = row - zh * 10;
             const int ih = h0 - 1 + zh, iw = w0 - 1 + zw;
-            const bool ok = row < SW_ROWS && (unsigned)d < (unsigned)n && (unsigned)ih < (unsigned)n && (unsigned)iw < (unsigned)n;
+            const bool ok = row < FL_ROWS && (unsigned)d < (unsigned)n && (unsigned)ih < (unsigned)n && (unsigned)iw < (unsigned)n;
             const int g = (lane & 3) ^ ((row >> 2) & 3);
-            const unsigned vo = ok ? (unsigned)((((((b << li) + d) << li) + ih) << li) + iw) * F8B_CIN + g * 16 : 0xFFFFFFF0u;
+            const unsigned vo = ok ? (unsigned)((((((b << li) + d) << li) + ih) << li) + iw) * FL_CIN + g * 16 : 0xFFFFFFF0u;
             vv_dma16(rs, vo, piece < 7 ? ldsx + (d % S8_NX) * S8_XB + piece * 1024 : ldsx + S8_NX * S8_XB);
         }
     };
@@ -65,7 +67,7 @@ __global__ __launch_bounds__(256, 2) void final_bce_sweep_fp8_kernel(const unsig
     const int nt = wv & 1, mt0 = wv >> 1;
     i32x8 fbv;
     {
-        const float *wr = w + (nt * 32 + fr) * F8B_CIN + 32 * fh;
+        const float *wr = w + (nt * 32 + fr) * FL_CIN + 32 * fh;
         f32x4 wq[8];
         float mx = 0.f;
 #pragma unroll
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(256, 2) void final_bce_sweep_fp8_kernel(const unsig
         for (int q = 0; q < 8; ++q) fbv[q] = (int)vv_pack_fp8x4(wq[q] * inv);
         if (wv < 2 && fh == 0) tsc[nt * 32 + fr] = s;
     }
-    for (int i = tid; i < SW_PSZ; i += 256) PH[i] = 0.f;         // P_{-1} = 0
+    for (int i = tid; i < S8_PSZ; i += 256) PH[i] = 0.f;         // P_{-1} = 0
 
     // gather role: s = od parity slot, ohh = output row inside the tile, mw = cell column (both pw per lane)
     const int mw = tid & 7, ohh = (tid >> 3) & 15, sl = tid >> 7;
@@ -99,7 +101,7 @@ __global__ __launch_bounds__(256, 2) void final_bce_sweep_fp8_kernel(const unsig
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[j][q] = 0.f;
             const int row = (mt0 + 2 * j) * 32 + fr;
-            const char *pa = Xd + row * F8B_CIN + (((fh * 2) ^ ((row >> 2) & 3)) << 4);
+            const char *pa = Xd + row * FL_CIN + (((fh * 2) ^ ((row >> 2) & 3)) << 4);
             const uint4 lo4 = *reinterpret_cast<const uint4 *>(pa);
             const uint4 hi4 = *reinterpret_cast<const uint4 *>(Xd + ((unsigned)(pa - Xd) ^ 16u));
             const i32x8 xv = {(int)lo4.x, (int)lo4.y, (int)lo4.z, (int)lo4.w, (int)hi4.x, (int)hi4.y, (int)hi4.z, (int)hi4.w};
@@ -125,20 +127,20 @@ __global__ __launch_bounds__(256, 2) void final_bce_sweep_fp8_kernel(const unsig
     for (int d = 0; d <= n; ++d) {
         // weights-first: lane = cell row, registers walk the taps of the half; quad g = taps 8g + 4fh .. +3 = the four tw
         // of one (td, th): one 16-byte store per quad
-        float *Pw = nt == 0 ? PL : PH + (oldh ^ 1) * SW_PSZ;
+        float *Pw = nt == 0 ? PL : PH + (oldh ^ 1) * S8_PSZ;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int row = (mt0 + 2 * j) * 32 + fr;
-            if (row < SW_ROWS) {
+            if (row < FL_ROWS) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<f32x4 *>(Pw + row * SW_PP + 8 * g + 4 * fh) =
+                    *reinterpret_cast<f32x4 *>(Pw + row * S8_PP + 8 * g + 4 * fh) =
                         f32x4{acc[j][4 * g] * tsv[g][0], acc[j][4 * g + 1] * tsv[g][1], acc[j][4 * g + 2] * tsv[g][2], acc[j][4 * g + 3] * tsv[g][3]};
             }
         }
         const int od = 2 * d - 1 + sl;
         const bool ovalid = (unsigned)od < (unsigned)n2;
-        const size_t o = ((((((size_t)b << lo) + (ovalid ? od : 0)) << lo) + oh) << lo) + ow;
+        const size_t o = fl_out_index(b, ovalid ? od : 0, oh, ow, lo);
         // The target pair is loaded by inline asm so that its wait can be counted: the vector-memory counter retires in
         // order, and a compiler-placed wait for this load would be vmcnt(0), i.e. it would also wait for the 2 pieces of
         // plane d+2 issued right after it -- the look-ahead.  In flight, oldest first:
@@ -154,14 +156,14 @@ __global__ __launch_bounds__(256, 2) void final_bce_sweep_fp8_kernel(const unsig
         mfma_plane(d + 1, acc_next);
 
         float l0 = 0.f, l1 = 0.f;
-        const float *Pold = PH + oldh * SW_PSZ;
+        const float *Pold = PH + oldh * S8_PSZ;
 #pragma unroll
         for (int ah = 0; ah < 2; ++ah) {
             const int zh = mh + ph - ah + 1, th = 1 - ph + 2 * ah;
-            const int off = (zh * 10 + mw) * SW_PP + (sl * 4 + th) * 4;
+            const int off = (zh * 10 + mw) * S8_PP + (sl * 4 + th) * 4;
             const float *r0 = PL + off, *r1 = Pold + off;
-            l0 += r0[SW_PP + 1] + r0[3] + r1[SW_PP + 1] + r1[3];                         // pw = 0
-            l1 += r0[2 * SW_PP] + r0[SW_PP + 2] + r1[2 * SW_PP] + r1[SW_PP + 2];   // pw = 1
+            l0 += r0[S8_PP + 1] + r0[3] + r1[S8_PP + 1] + r1[3];                         // pw = 0
+            l1 += r0[2 * S8_PP] + r0[S8_PP + 2] + r1[2 * S8_PP] + r1[S8_PP + 2];   // pw = 1
         }
         asm volatile("s_waitcnt vmcnt(2)" : "+v"(y) : : "memory");   // y has landed; plane d+2 may still be in flight
         if (ovalid) {
@@ -184,12 +186,8 @@ __global__ __launch_bounds__(256, 2) void final_bce_sweep_fp8_kernel(const unsig
         __syncthreads();      // every gather of P_d / P_{d-1} and every read of plane d+1 is done: publish d+1, refill its slot
     }
     vv_wait_vm<0>();                                             // the last (all-zero) look-ahead planes
-    bce = vv_wave_sum(bce); tp = vv_wave_sum(tp); fp = vv_wave_sum(fp); fn = vv_wave_sum(fn);
-    if (lane == 0) { red[wv][0] = bce; red[wv][1] = tp; red[wv][2] = fp; red[wv][3] = fn; }
-    __syncthreads();
-    if (tid < 4) partials[((size_t)b * ntile + tile) * 4 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    FL_BLOCK_STATS(bce, tp, fp, fn, tid, wv, red, partials, (size_t)b * ntile + tile);
 }
-
 
 }  // namespace
 
@@ -200,6 +198,6 @@ int vv_final_bce_sweep_fp8_launch(const void *x, const float *w_keras, const flo
     vv_allow_lds<&final_bce_sweep_fp8_kernel>(S8_LDS);
     const int ntile = (side / 8) * (side / 8);
     VV_LAUNCH(final_bce_sweep_fp8_kernel, dim3(ntile * batch), dim3(256), S8_LDS, st, reinterpret_cast<const unsigned char *>(x), w_keras, target,
-              probs, logits, partials, vv_log2(side), (unsigned)((size_t)batch * side * side * side * F8B_CIN), gamma, epsilon);
+              probs, logits, partials, vv_log2(side), (unsigned)((size_t)batch * side * side * side * FL_CIN), gamma, epsilon);
     return ntile;
 }

@@ -8,29 +8,11 @@
 // (<= 8 float32 grids per object) and final_mean_finish_kernel forms the mean and scores it.  Every sum runs in a fixed order that depends
 // on (K, side) only -- k ascending inside a slice, slices ascending, 1,024-voxel stats blocks in order -- and not on the number of objects
 // in the call: no float atomics, two runs are bit-identical, and an object's result does not depend on what it is batched with.
-#include "common.h"
+// The box geometry and staging, the Q-form sweep pieces, the voxel loss and the block reduction are the single-sample layer's
+// (final_common.h): a sample's probability is the same expression here and there.
+#include "final_common.h"
 
 namespace {
-
-constexpr int FM_CIN = 64;
-constexpr int FM_ROW = FM_CIN + 4;      // floats per staged voxel row of the box form (+16 B pad)
-
-// binary_loss / voxelPrecisionRecall terms of one averaged voxel (function.py:79-80, 110)
-__device__ __forceinline__ void fm_voxel_stats(float p, float y, float gamma, float epsilon, float &bce, float &tp, float &fp, float &fn) {
-    const float q = fminf(fmaxf(p, epsilon), 1.0f - epsilon);
-    bce -= gamma * y * logf(q) + (1.0f - gamma) * (1.0f - y) * logf(1.0f - q);
-    const float yh = p >= 0.5f ? 1.f : 0.f;
-    tp += y * yh; fp += (1.f - y) * yh; fn += y * (1.f - yh);
-}
-
-// wave shuffles, then the four waves in order: one (bce, TP, FP, FN) partial per workgroup
-__device__ __forceinline__ void fm_block_stats(float bce, float tp, float fp, float fn, float (*red)[4], float *dst) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    bce = vv_wave_sum(bce); tp = vv_wave_sum(tp); fp = vv_wave_sum(fp); fn = vv_wave_sum(fn);
-    if (lane == 0) { red[wv][0] = bce; red[wv][1] = tp; red[wv][2] = fp; red[wv][3] = fn; }
-    __syncthreads();
-    if (threadIdx.x < 4) dst[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
 
 // Where the sums go: the float32 probability sums of K slice s to part + s * slice_stride; the finish kernel adds the slices in order,
 // stores the mean and (with a target) one stats partial per 1,024 voxels.
@@ -45,57 +27,34 @@ struct FmOut {
 };
 
 // ---------------------------------------------------------------------------------------------------------------
-// Box form (float32 and bf16 activations, any side): the workgroup of first_last.hip's final_bce_kernel -- a 4x4x4 block of input
+// Box form (float32 and bf16 activations, any side): the workgroup of final_bce.hip's final_bce_kernel -- a 4x4x4 block of input
 // cells -> 8x8x8 outputs, wave = output parity (pd, ph), lane = cell with both pw -- looped over the samples [k0, k1) of its object
 // with the two probability sums in registers.  The weights sit in LDS; with bf16 activations they are rounded to bf16 first, as the
 // MFMA forms of the single-sample layer do, so that a sample's logit is the same product sum here and there.
-constexpr int FMB_LDS = (216 * FM_ROW + 64 * FM_CIN) * 4;
+constexpr int FMB_LDS = (216 * FL_BOX_ROW + 64 * FL_CIN) * 4;
 
 template <typename T>
 __global__ __launch_bounds__(256) void final_mean_box_kernel(const T *__restrict__ x, const float *__restrict__ w, FmOut a, int din_log2) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float *tile = reinterpret_cast<float *>(smem);                // [216][FM_ROW]
-    float *wl = tile + 216 * FM_ROW;                              // [64 taps][64 ci]
-    const int li = din_log2, n = 1 << li, nb = n >> 2;
+    float *tile = reinterpret_cast<float *>(smem);                // [216][FL_BOX_ROW]
+    float *wl = tile + 216 * FL_BOX_ROW;                              // [64 taps][64 ci]
+    const int li = din_log2, nb = (1 << li) >> 2;
     const int blk = blockIdx.x, b = blockIdx.y / a.nslices, s = blockIdx.y % a.nslices;
     const int k0 = (s * a.samples) / a.nslices, k1 = ((s + 1) * a.samples) / a.nslices;
-    const int bw = blk % nb, bh = (blk / nb) % nb, bd = blk / (nb * nb);
-    const int m0d = bd * 4, m0h = bh * 4, m0w = bw * 4;
 
-    for (int i = threadIdx.x; i < 64 * FM_CIN; i += 256) {
+    for (int i = threadIdx.x; i < 64 * FL_CIN; i += 256) {
         const float v = w[i];
         wl[i] = sizeof(T) == 2 ? static_cast<float>(static_cast<__bf16>(v)) : v;
     }
 
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int pd = wv >> 1, ph = wv & 1;
-    const int mw = lane & 3, mh = (lane >> 2) & 3, md = lane >> 4;
-    constexpr int EPL = 16 / sizeof(T);          // elements per 16-byte load
-    constexpr int LPV = FM_CIN / EPL;            // loads per voxel
+    const FlBox g = fl_box(blk, nb, wv, lane);
+    const int pd = g.pd, ph = g.ph, mw = g.mw, mh = g.mh, md = g.md;
     float sum0 = 0.f, sum1 = 0.f;
     for (int k = k0; k < k1; ++k) {
-        const T *xb = x + (((size_t)b * a.samples + k) << (3 * li)) * FM_CIN;
         __syncthreads();                          // the previous sample's tile is no longer read
-        for (int i = threadIdx.x; i < 216 * LPV; i += 256) {
-            const int vox = i / LPV, part = i % LPV;
-            const int zw = vox % 6, zh = (vox / 6) % 6, zd = vox / 36;
-            const int id = m0d - 1 + zd, ih = m0h - 1 + zh, iw = m0w - 1 + zw;
-            float vals[EPL];
-            if ((unsigned)id < (unsigned)n && (unsigned)ih < (unsigned)n && (unsigned)iw < (unsigned)n) {
-                const T *src = xb + ((((size_t)id << li) + ih << li) + iw) * FM_CIN + part * EPL;
-                const uint4 raw = *reinterpret_cast<const uint4 *>(src);
-                const T *rv = reinterpret_cast<const T *>(&raw);
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) vals[e] = static_cast<float>(rv[e]);
-            } else {
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) vals[e] = 0.f;
-            }
-            float *dst = tile + vox * FM_ROW + part * EPL;
-#pragma unroll
-            for (int e = 0; e < EPL; e += 4) *reinterpret_cast<f32x4 *>(dst + e) = f32x4{vals[e], vals[e + 1], vals[e + 2], vals[e + 3]};
-        }
+        fl_box_stage(x + (((size_t)b * a.samples + k) << (3 * li)) * FL_CIN, tile, g, li);
         __syncthreads();
         float acc0 = 0.f, acc1 = 0.f;
 #pragma unroll
@@ -104,15 +63,15 @@ __global__ __launch_bounds__(256) void final_mean_box_kernel(const T *__restrict
             for (int ah = 0; ah < 2; ++ah) {
                 const int zd = md + pd - ad + 1, zh = mh + ph - ah + 1;
                 const int td = 1 - pd + 2 * ad, th = 1 - ph + 2 * ah;
-                const float *r0 = tile + ((zd * 6 + zh) * 6 + mw) * FM_ROW;   // zw = mw, mw+1, mw+2
-                const float *wt = wl + ((td * 4 + th) * 4) * FM_CIN;          // [tw][ci], wave-uniform: LDS broadcast reads
+                const float *r0 = tile + ((zd * 6 + zh) * 6 + mw) * FL_BOX_ROW;   // zw = mw, mw+1, mw+2
+                const float *wt = wl + ((td * 4 + th) * 4) * FL_CIN;          // [tw][ci], wave-uniform: LDS broadcast reads
 #pragma unroll 4
-                for (int c = 0; c < FM_CIN; c += 4) {
+                for (int c = 0; c < FL_CIN; c += 4) {
                     const f32x4 x0 = *reinterpret_cast<const f32x4 *>(r0 + c);
-                    const f32x4 x1 = *reinterpret_cast<const f32x4 *>(r0 + FM_ROW + c);
-                    const f32x4 x2 = *reinterpret_cast<const f32x4 *>(r0 + 2 * FM_ROW + c);
-                    const f32x4 w0 = *reinterpret_cast<const f32x4 *>(wt + 0 * FM_CIN + c), w1 = *reinterpret_cast<const f32x4 *>(wt + 1 * FM_CIN + c);
-                    const f32x4 w2 = *reinterpret_cast<const f32x4 *>(wt + 2 * FM_CIN + c), w3 = *reinterpret_cast<const f32x4 *>(wt + 3 * FM_CIN + c);
+                    const f32x4 x1 = *reinterpret_cast<const f32x4 *>(r0 + FL_BOX_ROW + c);
+                    const f32x4 x2 = *reinterpret_cast<const f32x4 *>(r0 + 2 * FL_BOX_ROW + c);
+                    const f32x4 w0 = *reinterpret_cast<const f32x4 *>(wt + 0 * FL_CIN + c), w1 = *reinterpret_cast<const f32x4 *>(wt + 1 * FL_CIN + c);
+                    const f32x4 w2 = *reinterpret_cast<const f32x4 *>(wt + 2 * FL_CIN + c), w3 = *reinterpret_cast<const f32x4 *>(wt + 3 * FL_CIN + c);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         // pw = 0: i = mw (tw 1), mw-1 (tw 3);  pw = 1: i = mw+1 (tw 0), mw (tw 2)
@@ -124,19 +83,14 @@ __global__ __launch_bounds__(256) void final_mean_box_kernel(const T *__restrict
                 }
             }
         }
-        sum0 += 1.0f / (1.0f + expf(-acc0));                      // tf.sigmoid, autoencoder3D.py:136; the mean is over probabilities
-        sum1 += 1.0f / (1.0f + expf(-acc1));
+        sum0 += fl_sigmoid<FL_PRECISE>(acc0);                     // the mean is over probabilities
+        sum1 += fl_sigmoid<FL_PRECISE>(acc1);
     }
-    const int lo = li + 1;
-    const int od = 2 * (m0d + md) + pd, oh = 2 * (m0h + mh) + ph, ow = 2 * (m0w + mw);
-    const size_t o = ((((size_t)b << lo) + od << lo) + oh << lo) + ow;
-    *reinterpret_cast<float2 *>(a.part + (size_t)s * a.slice_stride + o) = make_float2(sum0, sum1);
+    *reinterpret_cast<float2 *>(a.part + (size_t)s * a.slice_stride + g.out(b, li)) = make_float2(sum0, sum1);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// (The staging offsets, weight-operand layout, mfma_plane, qkey, Q publish and gather below are final_bce_sweepw_kernel's, kept as a copy so that
-// the benchmarked single-sample kernel's generated code does not move; a layout change there belongs here too.)
-// Sweep form (bf16 activations, side >= 8): first_last.hip's final_bce_sweepw_kernel -- an 8 x 8 tile of cells in (h, w) swept through
+// Sweep form (bf16 activations, side >= 8): final_bce.hip's final_bce_sweepw_kernel (the Q form of final_common.h) -- an 8 x 8 tile of cells in (h, w) swept through
 // the depth, the 10 x 10 halo rows of a plane staged once by LDS-DMA into a two-slot ring, Q_d[centre cell][td][th][pw] formed on
 // v_mfma_f32_16x16x32_bf16 with the w direction summed inside the MFMA, od = 2d - 1 + s <- Q_d[td = s] + Q_{d-1}[td = 2 + s] -- run
 // over the (sample, plane) sequence of one object as ONE software pipeline: the plane after a sample's last one is the next sample's
@@ -145,20 +99,19 @@ __global__ __launch_bounds__(256) void final_mean_box_kernel(const T *__restrict
 // every sample (one halo plane in front: its Q only feeds the carry; plane n is the all-zero plane that closes a sweep).  Each thread
 // keeps the float32 probability sums of ITS output pairs in LDS (rng * 2 KB, thread-private slots: no barrier protects them, none is
 // needed).  Nothing but the LDS-DMA touches the vector-memory counter inside the loop, so "all but the newest 4" is plane t + 1.
-constexpr int MS_XB = 13 * 1024, MS_NX = 2, MS_ROWS = 100;
-constexpr int MS_BASE = MS_NX * MS_XB + 1024 + 80 * 128;       // plane ring + sink + Q
+static_assert(FL_NX == 2, "final_mean_sweep_kernel counts its waits and flips its ring for two plane slots");
+constexpr int MS_BASE = FL_NX * FL_XB + 1024 + FL_QB;          // plane ring + sink + Q
 static inline size_t ms_lds(int rng) { return (size_t)MS_BASE + (size_t)rng * 2048; }
 
 __global__ __launch_bounds__(256, 2) void final_mean_sweep_kernel(const __bf16 *__restrict__ x, const float *__restrict__ w, FmOut a, int din_log2,
                                                                   int rng_log2, unsigned x_bytes) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char *Xs = smem;                                             // ring of MS_NX planes x [104 rows][128 B], slot-swizzled; 1 KiB sink
-    char *Pq = smem + MS_NX * MS_XB + 1024;                      // Q_d [80 centre cells][td 4][th 4][pw 2] float32, 8-byte granule g at g ^ key(cell)
+    char *Xs = smem;                                             // ring of FL_NX planes x [104 rows][128 B], slot-swizzled; 1 KiB sink
+    char *Pq = smem + FL_NX * FL_XB + 1024;                      // Q_d [80 centre cells][td 4][th 4][pw 2] float32, 8-byte granule g at g ^ key(cell)
     char *Acc = smem + MS_BASE;                                  // [2 rng output planes][16 oh][8 cells] float2 sums
     const int li = din_log2, n = 1 << li, nt8 = n >> 3, ntile = nt8 * nt8;
     const int rng = 1 << rng_log2, nranges = n >> rng_log2;
-    const int T = gridDim.x;
-    const int wi = (T & 7) ? (int)blockIdx.x : (int)(blockIdx.x & 7) * (T >> 3) + (int)(blockIdx.x >> 3);
+    const int wi = fl_work_item();
     const int tile = wi % ntile, r = (wi / ntile) % nranges, s = (wi / (ntile * nranges)) % a.nslices, b = wi / (ntile * nranges * a.nslices);
     const int k0 = (s * a.samples) / a.nslices, k1 = ((s + 1) * a.samples) / a.nslices;
     const int d_first = r == 0 ? 0 : r * rng - 1, d_last = (r + 1) * rng;
@@ -169,95 +122,30 @@ __global__ __launch_bounds__(256, 2) void final_mean_sweep_kernel(const __bf16 *
 
     const u32x4 rs = vv_make_rsrc(x, x_bytes);
     const unsigned ldsx = (unsigned)(unsigned long long)(lptr_t)Xs;
-    // 13 pieces of 8 rows per plane; every wave issues 4 (the 3 surplus ones go to the sink so that the vector-memory counter advances
-    // uniformly); rows >= 100, voxels outside the grid, planes outside [0, n) and everything past the last sample arrive as zeros (every
-    // lane out of range by its OFFSET, as in final_bce_sweepw_kernel).  The lane part of the offset is prepared once; sample and plane
-    // ride in soffset.
-    unsigned sv[4], sdst[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int piece = wv * 4 + i, row = piece * 8 + (lane >> 3);
-        const int zh = row / 10, zw = row - zh * 10;
-        const int ih = h0 - 1 + zh, iw = w0 - 1 + zw;
-        const bool ok = row < MS_ROWS && (unsigned)ih < (unsigned)n && (unsigned)iw < (unsigned)n;
-        const int g = (lane & 7) ^ (zw & 7);
-        sv[i] = ok ? (unsigned)((ih << li) + iw) * (FM_CIN * 2) + g * 16 : 0xFFFFFFF0u;
-        sdst[i] = piece < 13 ? (unsigned)(piece * 1024) : (unsigned)(MS_NX * MS_XB);
-    }
+    // rows >= 100, voxels outside the grid, planes outside [0, n) and everything past the last sample arrive as zeros (every lane out
+    // of range by its OFFSET, as in final_bce_sweepw_kernel).  The lane offsets are those of sample 0: sample and plane ride in soffset.
+    FL_Q_STAGE_LANES(0)
     int ks = k0, ds = d_first;                                   // the (sample, plane) the next stage() fetches; FM_NEXT_PLANE moves it on
 #define FM_NEXT_PLANE() do { const bool wrap_ = ds == d_last; ks += wrap_ ? 1 : 0; ds = wrap_ ? d_first : ds + 1; } while (0)
     auto stage = [&](int sp, int ks, int ds) {
         const bool din = ks < k1 && (unsigned)ds < (unsigned)n;
-        const unsigned soff = (unsigned)__builtin_amdgcn_readfirstlane(din ? ((((b * a.samples + ks) << li) + ds) << (2 * li)) * (FM_CIN * 2) : 0);
-        const unsigned slot = ldsx + sp * MS_XB;
+        const unsigned soff = (unsigned)__builtin_amdgcn_readfirstlane(din ? ((((b * a.samples + ks) << li) + ds) << (2 * li)) * (FL_CIN * 2) : 0);
+        const unsigned slot = ldsx + sp * FL_XB;
 #pragma unroll
         for (int i = 0; i < 4; ++i) vv_dma16(rs, din ? sv[i] : 0xFFFFFFF0u, soff, wv * 4 + i < 13 ? slot + sdst[i] : ldsx + sdst[i]);
     };
     stage(0, ks, ds);
     FM_NEXT_PLANE();
 
-    // weights as the first MFMA operand, exactly as final_bce_sweepw_kernel lays them out
-    const int c16 = lane & 15, kq = lane >> 4;
-    uint4 wf[2][4];
-#pragma unroll
-    for (int pw = 0; pw < 2; ++pw)
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int tw = pw == 0 ? (kk < 2 ? 1 : 3) : (kk < 2 ? 0 : 2);
-            const float *wr = w + (c16 * 4 + tw) * FM_CIN + (kk & 1) * 32 + kq * 8;
-            const f32x4 w0v = *reinterpret_cast<const f32x4 *>(wr), w1v = *reinterpret_cast<const f32x4 *>(wr + 4);
-            bf16x8 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { o[e] = static_cast<__bf16>(w0v[e]); o[4 + e] = static_cast<__bf16>(w1v[e]); }
-            wf[pw][kk] = *reinterpret_cast<const uint4 *>(&o);
-        }
-    const int ntl = wv == 0 ? 2 : 1;
-    const int rowC = (2 * wv + (c16 >> 3)) * 10 + 1 + (c16 & 7);
-    unsigned xo[3][2];
-#pragma unroll
-    for (int s3 = 0; s3 < 3; ++s3)
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-            const int sh = s3 == 0 ? 0 : s3 == 1 ? -1 : 1, zwc = 1 + (c16 & 7) + sh;
-            xo[s3][hf] = (unsigned)((rowC + sh) * 128 + (((hf * 4 + kq) ^ (zwc & 7)) << 4));
-        }
-    auto qkey = [](int pr) { return (((pr & 7) + (pr >> 3)) & 7) << 1; };
-
-    // gather role: sl = od parity slot, ohh = output row inside the tile, mw = cell column (both pw per lane)
-    const int mw = tid & 7, ohh = (tid >> 3) & 15, sl = tid >> 7;
-    const int mh = ohh >> 1, ph = ohh & 1;
-    const int lo = li + 1;
-    const int oh = 2 * h0 + ohh, ow = 2 * (w0 + mw);
+    FL_Q_OPERANDS(w)
+    const FlRole gr = fl_role(tid);
+    const int sl = gr.sl, lo = li + 1;
+    const int oh = gr.oh(h0), ow = gr.ow(w0);
     float2 *mine = reinterpret_cast<float2 *>(Acc) + (tid & 127);   // slot of local output plane q: mine[q * 128]; this thread owns q = 2j + 1 - sl
     for (int j = 0; j < rng; ++j) mine[(2 * j + 1 - sl) * 128] = make_float2(0.f, 0.f);
     float lo0 = 0.f, lo1 = 0.f;
 
-    auto mfma_plane = [&](int sp, f32x4 (&acc)[2][2]) {
-        const char *Xd = Xs + sp * MS_XB;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            acc[t][0] = f32x4{0.f, 0.f, 0.f, 0.f};
-            acc[t][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (t < ntl) {
-                const char *Xt = Xd + t * (80 * 128);
-                uint4 fc[2], fl[2], fr2[2];
-#pragma unroll
-                for (int hf = 0; hf < 2; ++hf) {
-                    fc[hf] = *reinterpret_cast<const uint4 *>(Xt + xo[0][hf]);
-                    fl[hf] = *reinterpret_cast<const uint4 *>(Xt + xo[1][hf]);
-                    fr2[hf] = *reinterpret_cast<const uint4 *>(Xt + xo[2][hf]);
-                }
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    const uint4 &a0 = kk < 2 ? fc[kk] : fl[kk - 2], &a1 = kk < 2 ? fr2[kk] : fc[kk - 2];
-                    acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8 *>(&wf[0][kk]),
-                                                                        *reinterpret_cast<const bf16x8 *>(&a0), acc[t][0], 0, 0, 0);
-                    acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8 *>(&wf[1][kk]),
-                                                                        *reinterpret_cast<const bf16x8 *>(&a1), acc[t][1], 0, 0, 0);
-                }
-            }
-        }
-    };
+    auto mfma_plane = [&](int sp, f32x4 (&acc)[2][2]) { fl_q_mfma_plane(Xs + sp * FL_XB, ntl, xo, wf, acc); };   // sp = ring slot of the plane
 
     vv_wait_vm<0>();                                             // step 0's plane
     __syncthreads();
@@ -271,14 +159,7 @@ __global__ __launch_bounds__(256, 2) void final_mean_sweep_kernel(const __bf16 *
     int oldh = 0, d = d_first;
 #pragma unroll 1
     for (int t = 0; t < nsteps; ++t) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-            if (u < ntl) {
-                const int pr = (wv + 4 * u) * 16 + c16, key = qkey(pr);
-                char *row = Pq + pr * 128;
-                *reinterpret_cast<f32x4 *>(row + (((4 * kq) ^ key) << 3)) = f32x4{acc[u][0][0], acc[u][1][0], acc[u][0][1], acc[u][1][1]};
-                *reinterpret_cast<f32x4 *>(row + (((4 * kq + 2) ^ key) << 3)) = f32x4{acc[u][0][2], acc[u][1][2], acc[u][0][3], acc[u][1][3]};
-            }
+        FL_Q_PUBLISH(Pq, acc)
         stage(oldh, ks, ds);                                     // step t + 2 into the slot step t's MFMAs have left
         FM_NEXT_PLANE();
         vv_wait_vm<4>();                                         // in flight: [step t+1 x4][step t+2 x4] -> step t + 1 has landed
@@ -291,22 +172,13 @@ __global__ __launch_bounds__(256, 2) void final_mean_sweep_kernel(const __bf16 *
         const bool first = d == d_first;                         // a sample starts: nothing is carried over from the previous one
         float l0 = first ? 0.f : lo0, l1 = first ? 0.f : lo1;
         lo0 = 0.f; lo1 = 0.f;
-#pragma unroll
-        for (int ah = 0; ah < 2; ++ah) {
-            const int zh = mh + ph - ah + 1, th = 1 - ph + 2 * ah;
-            const int pr = zh * 8 + mw, key = qkey(pr);
-            const char *row = Pq + pr * 128;
-            const float2 qa = *reinterpret_cast<const float2 *>(row + (((sl * 4 + th) ^ key) << 3));
-            const float2 qb = *reinterpret_cast<const float2 *>(row + ((((2 + sl) * 4 + th) ^ key) << 3));
-            l0 += qa.x; l1 += qa.y;
-            lo0 += qb.x; lo1 += qb.y;
-        }
+        FL_Q_GATHER(Pq, gr, l0, l1, lo0, lo1)
         const int od = 2 * d - 1 + sl;
         if (od >= od_lo && od < od_hi) {
             float2 *slot = mine + (od - od_lo) * 128;
             float2 v = *slot;
-            v.x += __builtin_amdgcn_rcpf(1.0f + __expf(-l0));    // the single-sample sweep form's sigmoid; the mean is over probabilities
-            v.y += __builtin_amdgcn_rcpf(1.0f + __expf(-l1));
+            v.x += fl_sigmoid<FL_HW>(l0);                        // the single-sample sweep form's sigmoid; the mean is over probabilities
+            v.y += fl_sigmoid<FL_HW>(l1);
             *slot = v;
         }
 #pragma unroll
@@ -321,7 +193,7 @@ __global__ __launch_bounds__(256, 2) void final_mean_sweep_kernel(const __bf16 *
     float *dst = a.part + (size_t)s * a.slice_stride;
     for (int j = 0; j < rng; ++j) {
         const int q = 2 * j + 1 - sl;
-        const size_t o = ((((((size_t)b << lo) + (od_lo + q)) << lo) + oh) << lo) + ow;
+        const size_t o = ((((((size_t)b << lo) + (od_lo + q)) << lo) + oh) << lo) + ow;   // not fl_out_index: as a call it reorders this epilogue
         *reinterpret_cast<float2 *>(dst + o) = mine[q * 128];
     }
 }
@@ -340,23 +212,10 @@ __global__ __launch_bounds__(256) void final_mean_finish_kernel(FmOut a, int vox
         if (a.target) {
             const f32x4 y = *reinterpret_cast<const f32x4 *>(a.target + o);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) fm_voxel_stats(p[e], y[e], a.gamma, a.epsilon, bce, tp, fp, fn);
+            for (int e = 0; e < 4; ++e) fl_voxel_stats<FL_PRECISE>(p[e], 0.f, y[e], a.gamma, a.epsilon, 1.0f - a.epsilon, false, bce, tp, fp, fn);
         }
     }
-    if (a.target) fm_block_stats(bce, tp, fp, fn, red, a.partials + ((size_t)b * gridDim.x + blockIdx.x) * 4);
-}
-
-// stats[b] = sum of the object's partials in block order
-__global__ __launch_bounds__(64) void final_mean_reduce_kernel(const float *__restrict__ partials, float *__restrict__ stats, int nparts) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = lane; i < nparts; i += 64) {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(partials + ((size_t)b * nparts + i) * 4);
-        s[0] += v[0]; s[1] += v[1]; s[2] += v[2]; s[3] += v[3];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s[k] = vv_wave_sum(s[k]);
-    if (lane == 0) *reinterpret_cast<f32x4 *>(stats + (size_t)b * 4) = f32x4{s[0], s[1], s[2], s[3]};
+    if (a.target) FL_BLOCK_STATS(bce, tp, fp, fn, (int)threadIdx.x, (int)(threadIdx.x >> 6), red, a.partials, (size_t)b * gridDim.x + blockIdx.x);
 }
 
 template <typename TA>
@@ -423,7 +282,7 @@ VV_EXPORT int vv_convT3d_final_mean_fwd(const void *x, const float *w_keras, con
                                         size_t workspace_bytes, void *stream) {
     if (!x || !w_keras || !mean_probs || (target != nullptr) != (stats != nullptr)) return VV_ERR_NULL;
     if (dtype != VV_F32 && dtype != VV_BF16) return VV_ERR_DTYPE;
-    if (objects <= 0 || samples < 1 || samples > 1024 || (long)objects * samples > 65535 || side < 4 || !vv_is_pow2(side) || cin != FM_CIN)
+    if (objects <= 0 || samples < 1 || samples > 1024 || (long)objects * samples > 65535 || side < 4 || !vv_is_pow2(side) || cin != FL_CIN)
         return VV_ERR_SHAPE;
     if (!vv_aligned16(x) || (target && !vv_aligned16(target)) || !vv_aligned16(mean_probs)) return VV_ERR_ALIGN;
     if (!workspace || workspace_bytes < vv_convT3d_final_mean_workspace_bytes(objects, samples, side) || !vv_aligned16(workspace))
@@ -441,7 +300,7 @@ VV_EXPORT int vv_convT3d_final_mean_fwd(const void *x, const float *w_keras, con
     if (p.sweep) {
         vv_allow_lds<&final_mean_sweep_kernel>((int)ms_lds(16));
         // 32-bit buffer offsets: <= 2 GiB of input per launch, cut by whole objects; every per-object tensor moves on by the same range
-        const size_t in_per = (size_t)side * side * side * FM_CIN * 2 * samples;
+        const size_t in_per = (size_t)side * side * side * FL_CIN * 2 * samples;
         const int per = vv_chunk_samples(in_per, objects);
         if (per < 1) return VV_ERR_SHAPE;
         const int ntile = (side / 8) * (side / 8), nranges = side / p.rng;
@@ -466,6 +325,6 @@ VV_EXPORT int vv_convT3d_final_mean_fwd(const void *x, const float *w_keras, con
         }
     }
     VV_LAUNCH(final_mean_finish_kernel, dim3((unsigned)p.nfin, (unsigned)objects), dim3(256), 0, st, a, (int)vox);
-    if (target) VV_LAUNCH(final_mean_reduce_kernel, dim3((unsigned)objects), dim3(64), 0, st, a.partials, stats, p.nfin);
+    if (target) vv_final_reduce_launch(a.partials, stats, p.nfin, objects, st);
     return vv_launch_status();
 }

@@ -22,7 +22,7 @@
 #include "common.h"
 
 int vv_first_conv_bf16_launch(const float *x, const void *w_packed, const float *scale, const float *shift, void *y, int batch,
-                              int side, int act, void *stream, int out_fp8);   // first_last.hip
+                              int side, int act, void *stream, int out_fp8);   // first_conv.hip
 
 namespace {
 

@@ -269,13 +269,7 @@ __global__ __launch_bounds__(256) void reparam_kl_kernel(const float *__restrict
 __global__ __launch_bounds__(64) void shape_metrics_kernel(const float *__restrict__ stats, float *__restrict__ out4, int batch) {
     const int lane = threadIdx.x;
     float bce = 0.f, pr = 0.f, rc = 0.f, iou = 0.f;
-    for (int b = lane; b < batch; b += 64) {
-        const float l = stats[b * 4 + 0], tp = stats[b * 4 + 1], fp = stats[b * 4 + 2], fn = stats[b * 4 + 3];
-        bce += l;
-        pr += tp / (tp + fp + 1e-10f);
-        rc += tp / (tp + fn + 1e-10f);
-        iou += tp / fmaxf(tp + fp + fn, 1.f);
-    }
+    for (int b = lane; b < batch; b += 64) vv_add_shape_metrics(stats[b * 4 + 0], stats[b * 4 + 1], stats[b * 4 + 2], stats[b * 4 + 3], bce, pr, rc, iou);
     bce = vv_wave_sum(bce); pr = vv_wave_sum(pr); rc = vv_wave_sum(rc); iou = vv_wave_sum(iou);
     if (lane == 0) {
         out4[0] = bce / batch; out4[1] = pr / batch; out4[2] = rc / batch; out4[3] = iou / batch;
@@ -456,10 +450,14 @@ VV_EXPORT int vv_reparam_kl_fwd(const float *enc_out, const float *eps, const fl
     return vv_launch_status();
 }
 
+void vv_shape_metrics_launch(const float *stats, float *out4, int batch, hipStream_t st) {
+    VV_LAUNCH(shape_metrics_kernel, dim3(1), dim3(64), 0, st, stats, out4, batch);
+}
+
 VV_EXPORT int vv_shape_metrics(const float *stats, float *out4, int batch, void *stream) {
     if (!stats || !out4) return VV_ERR_NULL;
     if (batch <= 0) return VV_ERR_SHAPE;
-    VV_LAUNCH(shape_metrics_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), stats, out4, batch);
+    vv_shape_metrics_launch(stats, out4, batch, reinterpret_cast<hipStream_t>(stream));
     return vv_launch_status();
 }
 

@@ -270,8 +270,8 @@ NO_SCRATCH = ('conv_direct_kernel', 'conv_direct16_kernel', 'conv_direct16h_kern
 # kernel family -> (source, VGPR budget): launchers that deal the work items for a fixed number of workgroups per CU.  The first layer's
 # plane form was written for four per CU (128 VGPRs); removing its timing ablations let the register allocator drift to 134 = three per
 # CU under a launcher that still dealt for four (a 1.33-round grid, ~20 % of the kernel) and nothing noticed for a round.
-RESIDENT_BUDGET = {'first_conv_chain_kernel': ('first_last.hip', 128), 'final_bce_sweep_kernel': ('first_last.hip', 168),
-                   'final_bce_sweepw_kernel': ('first_last.hip', 128)}
+RESIDENT_BUDGET = {'first_conv_chain_kernel': ('first_conv.hip', 128), 'final_bce_sweep_kernel': ('final_bce.hip', 168),
+                   'final_bce_sweepw_kernel': ('final_bce.hip', 128)}
 
 
 def family(mangled):

@@ -162,6 +162,25 @@ def test_one_sample_is_the_single_sample_layer(L, dtname, B, side):
         assert np.all(np.abs(s[:, k] - s1[:, k]) <= slack)
 
 
+@pytest.mark.parametrize('B,side', [(3, 8), (2, 16)])
+def test_one_sample_sweep_is_the_single_sample_sweep_bit_for_bit(L, B, side, monkeypatch):
+    """bf16, K = 1, both layers in their Q-form sweep (final_mean takes it for every bf16 call at side >= 8; the single-sample layer
+    is forced to it, small batches go to its box form otherwise): staging, operands, MFMAs, publish, gather and sigmoid are one text
+    in final_common.h, so the mean of one sample IS the single-sample probability, bit for bit."""
+    monkeypatch.setenv('VV_FINAL_BCE', 'sweep')
+    x, w, y = _op_inputs('bf16', B, 1, side)
+    D = 2 * side
+    xd, wd, yd = _dev(x, torch.bfloat16), _dev(w), _dev(y)
+    got, _ = _final_mean(L, xd, wd, yd, B, 1, side, L.VV_BF16)
+    ws = torch.empty(max(L.load().vv_convT3d_final_bce_workspace_bytes(B, side), 16), dtype=torch.uint8, device=DEV)
+    probs = torch.full((B, D, D, D, 1), -1.0, dtype=torch.float32, device=DEV)
+    stats = torch.empty(B, 4, dtype=torch.float32, device=DEV)
+    L.call('vv_convT3d_final_bce_fwd', L.ptr(xd), L.ptr(wd), L.ptr(yd), L.ptr(probs), None, L.ptr(stats), B, side, 64, 0.6, 1e-7, L.VV_BF16,
+           L.ptr(ws), ws.numel(), _st())
+    torch.cuda.synchronize()
+    assert np.array_equal(got, probs.cpu().numpy())
+
+
 @pytest.mark.parametrize('B,K,Lz', [(3, 5, 64), (1, 32, 16), (7, 1, 64)])
 def test_sample_latents(L, B, K, Lz):
     rng = np.random.default_rng(B * 100 + K)
