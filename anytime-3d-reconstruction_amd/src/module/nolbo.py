@@ -419,6 +419,20 @@ class _ModelnetBase(object):
         pred = self.getSampledShape(mean, logvar, sampling_num, _eps=_eps)
         return voxel_points(pred, dims, pose, prob=prob, surface_only=surface_only)
 
+    def getSampledObjects(self, mean, logvar, bbox2D, bbox3D, sin, cos, image_size, sampling_num=32, proj_mat=None, proj_mat_inv=None,
+                          prob=0.5, surface_only=False, *, _eps=None):
+        """Detections in, posed point clouds out: getSampledShape for every detection's latent, voxvae.pose.object_poses for the
+        detections' boxes and angles, then ObjectPoses.points on the kept ones -- what a caller of the reference's
+        nolbo_test.getPred(...) followed by visualizer.getObjectInRealWorld(...) gets, without a grid or a pose leaving the device.
+        mean / logvar [n,L]; bbox2D [n,5] normalised, bbox3D [n,3] = (w, h, l), sin / cos [n,3]; image_size = (cols, rows); proj_mat
+        None: the KITTI matrix.  Returns (ObjectPoses, PointCloud or None when nothing is kept); the 4-byte count of kept detections
+        and the cloud's 8-byte total are what is read back."""
+        from voxvae.pose import KITTI_PROJ_MAT, object_poses
+        pred = self.getSampledShape(mean, logvar, sampling_num, _eps=_eps)
+        poses = object_poses(self._dev(bbox2D), self._dev(bbox3D), self._dev(sin), self._dev(cos), image_size,
+                             KITTI_PROJ_MAT if proj_mat is None else proj_mat, proj_mat_inv)
+        return poses, poses.points(pred, prob=prob, surface_only=surface_only)
+
     # ---------------------------------------------------------------- precision / recall curves (an extension)
     def getPRCurve(self, inputs, curve, category_vectors=None, missing_prob=0.0, sampling_num=0, corrected=None, *, group=None,
                    training=False, _eps=None, _mask=None, _eps2=None):

@@ -95,6 +95,13 @@ SIGNATURES = {
     'vv_voxel_points_workspace_bytes': (_sz, [_i, _i]),
     'vv_voxel_points_count': (_i, [_vp, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'vv_voxel_points_emit': (_i, [_vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _sz, _i, _i, _vp]),
+    'vv_object_pose_workspace_bytes': (_sz, [_i]),
+    'vv_object_pose': (_i, [_vp] * 4 + [_i, ctypes.c_double, ctypes.c_double] + [_vp] * 12 + [_sz, _vp]),
+    'vv_object_pose_host': (_i, [_vp] * 4 + [_i, ctypes.c_double, ctypes.c_double] + [_vp] * 12 + [_i]),
+    'vv_pose_translation_host': (_i, [_vp] * 7),
+    'vv_pose_ray_host': (_i, [_vp, ctypes.c_double, ctypes.c_double, _vp]),
+    'vv_pose_ray_rotation_host': (_i, [_vp, _vp]),
+    'vv_pose_box_projection_host': (_i, [_vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp]),
     'vv_latent_mask_fill':(_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     'vv_nearest_category': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     'vv_latent_correct': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

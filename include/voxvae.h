@@ -376,6 +376,50 @@ int vv_voxel_points_emit(const void *occ, int packed, float prob, int surface_on
                          size_t workspace_bytes, int batch, int side, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Detections -> posed objects (object_pose.hip, pose_solve.h): getObjectInRealWorld of src/visualizer/visualizer.py:237-308 without its
+ * point-cloud step (that is vv_voxel_points_*), for n detections of one frame and one camera.  Per detection: the "too close" pre-filter
+ * on the normalised box (x1 > 0.1, x2 < 0.9, y2 < 0.9), pixel scaling, the -5 degree elevation correction, R = RA RE RI in kitti axes,
+ * the ray rotation through the box centre, the translation fit of getTranslation (:79-146: 128 corner-to-box-edge assignments k, in the
+ * loop nest's execution order; per k the right singular vector of the smallest singular value of a 4x4 matrix, the reference's
+ * acceptance tests, the IoU of the reprojected box; the largest IoU wins, ties go to the lowest k), the 4x4 pose, the eight projected
+ * corners, the post-filter X[2] > 0.1.  All arithmetic is float64; the interface is float32 / int32.
+ *   bbox2d      float32 [n][5] = (x1, y1, x2, y2, objectness), normalised;  bbox3d float32 [n][3] = (w, h, l);
+ *   sin_aei / cos_aei   float32 [n][3] = sine / cosine of (azimuth, elevation, in-plane rotation).  A detection with a NaN among these
+ *               14 numbers is not kept (candidate -2).
+ *   image_col, image_row   the image size in pixels;  proj / proj_inv: HOST pointers to 16 doubles each (row-major 4x4), read during the
+ *               call and passed to the kernel by value -- also by vv_object_pose, whose other pointers are device pointers.
+ *   n           1 .. 65536.
+ *   per detection i:  keep int32 [n] (0 / 1);  candidate int32 [n] = the winning k, -1 when every candidate was rejected (translation 0),
+ *               -2 when the detection did not reach the fit;  iou float32 [n] = the winner's IoU (-1 without one).
+ *   compacted, row r = the r-th kept detection in input order:  count int32 [1];  index int32 [n] = its i;  pose float32 [n][16];
+ *               size float32 [n][3] = (h, l, w);  box2d int32 [n][4] = the pixel box truncated toward zero;  box3d_proj float32 [n][16] =
+ *               [2][2][2][2] in the reference's (i, j, k, xy) order.  Rows at or past count are not written.
+ * vv_object_pose: two launches on `stream` (a wave per detection; one workgroup compacting with ballots and population counts: no
+ * atomics, no sort, the same bits on every run); workspace of vv_object_pose_workspace_bytes(n) bytes (0 for a refused n).
+ * vv_object_pose_host: the same code compiled for the CPU, every pointer a host pointer, no stream, no workspace; `translation`, when
+ * not NULL, receives the float64 translation of every detection, float64 [n][3] (zeros without a winner); sweeps > 0 overrides the
+ * solver's number of Jacobi sweeps (<= 64; 0: the built-in count, which the device always uses).
+ * Pointers need the alignment of their element type and no more. */
+size_t vv_object_pose_workspace_bytes(int n);
+int vv_object_pose(const float *bbox2d, const float *bbox3d, const float *sin_aei, const float *cos_aei, int n, double image_col,
+                   double image_row, const double *proj, const double *proj_inv, int *keep, int *candidate, float *iou, int *count,
+                   int *index, float *pose, float *size, int *box2d, float *box3d_proj, void *workspace, size_t workspace_bytes,
+                   void *stream);
+int vv_object_pose_host(const float *bbox2d, const float *bbox3d, const float *sin_aei, const float *cos_aei, int n, double image_col,
+                        double image_row, const double *proj, const double *proj_inv, int *keep, int *candidate, float *iou, int *count,
+                        int *index, float *pose, float *size, int *box2d, float *box3d_proj, double *translation, int sweeps);
+/* The reference's single-object helpers from the same header, on the host, float64 in and out (row-major matrices):
+ * getTranslation(proj, R [9], (x_min, y_min, x_max, y_max) in pixels, (w, h, l)) -> translation [3] (zeros without a winner), and when
+ * not NULL the winning k (-1: none) and its IoU;  getRay(proj_inv, (px, py)) -> unit ray [3];  getRayRotation(ray) -> R [9];
+ * get3DbboxProjection(proj, R, t, w, h, l) -> corners [2][2][2][2]. */
+int vv_pose_translation_host(const double *proj, const double *rotation, const double *box2d, const double *whl, double *translation,
+                             int *candidate, double *iou);
+int vv_pose_ray_host(const double *proj_inv, double px, double py, double *ray);
+int vv_pose_ray_rotation_host(const double *ray, double *rotation);
+int vv_pose_box_projection_host(const double *proj, const double *rotation, const double *translation, double w, double h, double l,
+                                double *corners);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Training path (nolboSingleObject_modelnet_category_{VAE,AE}.fit, nolbo.py:1411-1447 / 1230-1258).  float32.
  * Data gradients reuse the forward kernels: d(Conv3D k4 s2)/d(input) = vv_convT3d_k4s2_fwd with the SAME Keras
  * kernel array packed by vv_pack_convT_k4s2 (read as [4,4,4,Cout_T = Cin, Cin_T = Cout]); d(Conv3DTranspose k4 s2)/
