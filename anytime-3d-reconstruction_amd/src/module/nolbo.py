@@ -59,20 +59,36 @@ class _ModelnetBase(object):
         x = self._dev(a)
         return x, (x if b is a else self._dev(b))
 
-    def _to_act(self, z):
-        return z if self._act_dt == _L.VV_F32 else z.to(torch.bfloat16)
+    def _draw_eps(self, B, eps=None):
+        """A sampling / prior epsilon [B,L]: torch.randn for the reference's tf.random.normal (nolbo.py:1470, 1508) unless injected."""
+        return torch.randn(B, self._latent_dim, dtype=torch.float32, device=self._device) if eps is None else self._dev(eps)
 
-    def _encode_latent(self, x, eps=None, want_kl=False):
-        """encoder -> (slice | clip | sampling) for the VAE, identity for the AE.  Returns (z, z_act, kl)."""
-        enc_out = self._enc_eng.forward(x)
-        if not self._variational:
-            return enc_out, self._to_act(enc_out), None
+    def _draw_mask(self, B, missing_prob, mask=None):
+        """The missing-latent mask [B,L] (1 = kept): reference nolbo.py:1475-1476, same RNG call, unless injected."""
+        if mask is None:
+            Lz = self._latent_dim
+            mask = np.reshape(np.random.choice(2, B * Lz, p=[missing_prob, 1. - missing_prob]), [B, Lz]).astype('float32')
+        return self._dev(mask)
+
+    def _enc_out(self, x, training=False):
+        """What the latent is formed from: the voxel encoder's output (the image -> 3D model: its 2D encoder's)."""
+        return self._enc_eng.forward(x)
+
+    def _reparam(self, enc_out, eps=None, act_dt=None, want_stats=False):
+        """(mean | logVar) [B,2L] -> slice | clip | sampling | KL (nolbo.py:1417-1420, 1464-1470) through vv_reparam_kl_fwd.
+        Returns (z, z_act, kl, mean, clipped logVar), the last two None without want_stats."""
         Lz = self._latent_dim
-        if enc_out.shape[1] != 2 * Lz:
-            raise ValueError('VAE encoder must emit 2*z_category_dim channels, got %d' % enc_out.shape[1])
-        eps = torch.randn(x.shape[0], Lz, dtype=torch.float32, device=self._device) if eps is None else self._dev(eps)
-        z, z_act, kl, _, _ = _E.reparam_kl(enc_out, eps, Lz, self._act_dt)
-        return z, z_act, kl
+        if enc_out.dim() != 2 or enc_out.shape[1] != 2 * Lz:
+            raise ValueError('the encoder must emit [B, %d] (mean | logVar), got %s' % (2 * Lz, tuple(enc_out.shape)))
+        return _E.reparam_kl(enc_out, self._draw_eps(enc_out.shape[0], eps), Lz, self._act_dt if act_dt is None else act_dt,
+                             want_stats=want_stats)
+
+    def _encode_latent(self, x, eps=None):
+        """encoder -> (slice | clip | sampling) for the VAE, identity for the AE.  Returns (z, z_act, kl)."""
+        enc_out = self._enc_out(x)
+        if not self._variational:
+            return enc_out, (enc_out if self._act_dt == _L.VV_F32 else enc_out.to(torch.bfloat16)), None
+        return self._reparam(enc_out, eps)[:3]
 
     def _decode_metrics(self, z_act, target, h1=None):
         out, _, stats, m = self._dec_eng.forward(z_act, target, want_metrics=True, h1=h1)
@@ -82,19 +98,58 @@ class _ModelnetBase(object):
         """encoder -> latent -> first decoder layer for the paths that decode the latent unchanged (getEval with
         missing_prob = 0, eval_forward_device): the fused latent tail when it applies, else the split calls.
         Returns (z, z_act, kl, h1 or None)."""
-        if _E.latent_tail_supported(self._enc_eng, self._dec_eng, self._variational):
+        if self._enc_eng is not None and _E.latent_tail_supported(self._enc_eng, self._dec_eng, self._variational):
             pos = _E.pos_latent_tail_supported(self._enc_eng, self._dec_eng, self._variational, x.shape[0])
             h = self._enc_eng.forward(x, stop_before_tail=True, stop_before_pos=pos)
             pos = pos and h.shape[1] == 4          # the layer in front of the tail was left to the fused call
-            if self._variational:
-                Lz = self._latent_dim
-                eps = torch.randn(x.shape[0], Lz, dtype=torch.float32, device=self._device) if eps is None else self._dev(eps)
-            else:
-                eps = None
+            eps = self._draw_eps(x.shape[0], eps) if self._variational else None
             z, z_act, kl, _, h1 = _E.latent_tail(self._enc_eng, self._dec_eng, h, eps, self._variational, pos_layer=pos)
             return z, z_act, kl, h1
-        z, z_act, kl = self._encode_latent(x, eps)
-        return z, z_act, kl, None
+        return self._encode_latent(x, eps) + (None,)
+
+    def _latent_training_mode(self, x, eps=None):
+        """_encode_decode_seed's counterpart for training=True: the trainer's encoder forward (batch statistics)."""
+        return self._train_helper().latent_training_mode(x, None if eps is None else self._dev(eps)) + (None,)
+
+    def _eval_hooks(self, training, seed=False):
+        """What differs between the forms of getEval: how the latent is obtained and how a latent is decoded.
+            latent(x, eps) -> (z, z_act, kl, h1 or None)        decode(z_act, y, h1) -> (prediction, stats [B,4], metrics [4])
+        Evaluation: the engines (seed: with the fused latent tail when it applies).  training=True (reference nolbo.py:1449, 1463,
+        1496: `self._encoder(x, training=training)`): the trainer's forward halves -- BatchNorm normalises with batch statistics and
+        moves the moving ones (momentum 0.99), no optimisation step.  In that mode the callers hand the decoder entry a FLOAT32 latent,
+        which it casts (one more vv_convert in bf16), even where an activation-dtype copy exists (the trainer's z_act, _zero_masked's twin),
+        and the latent ops write float32 only (`twin=False`): the launches of the copies this replaced, kept for identical results and
+        traces -- inherited, not something the algorithm needs."""
+        if training:
+            return self._latent_training_mode, lambda z_act, y, h1: self._train_helper().decoder_training_mode(z_act, y)
+        return (self._encode_decode_seed if seed else lambda x, eps: self._encode_latent(x, eps) + (None,)), self._decode_metrics
+
+    def _out_pair(self, z, twin):
+        """Buffers of a latent op's result: float32, the activation-dtype twin (the same tensor in f32 mode or without `twin`), its dtype code."""
+        act_dt = self._act_dt if twin else _L.VV_F32
+        o = torch.empty_like(z)
+        return o, (o if act_dt == _L.VV_F32 else torch.empty(z.shape, dtype=torch.bfloat16, device=self._device)), act_dt
+
+    def _mask_fill(self, z, mask, cats, twin=True):
+        """z * mask with the zeros replaced by the prototypes' column means (nolbo.py:1477-1482) -> (float32, activation dtype)."""
+        zf, zf_act, act_dt = self._out_pair(z, twin)
+        _L.call('vv_latent_mask_fill', _L.ptr(z), _L.ptr(mask), _L.ptr(cats), cats.shape[0], _L.ptr(zf),
+                None if zf_act is zf else _L.ptr(zf_act), act_dt, z.shape[0], z.shape[1], _st())
+        return zf, zf_act
+
+    def _latent_correct(self, z, mask, cats, idx, eps2, twin=True):
+        """The prior sample cats[idx] + eps2 wherever mask == 0, z elsewhere (nolbo.py:1507-1510) -> (float32, activation dtype)."""
+        zc, zc_act, act_dt = self._out_pair(z, twin)
+        _L.call('vv_latent_correct', _L.ptr(z), _L.ptr(mask), _L.ptr(cats), _L.ptr(idx), _L.ptr(eps2), _L.ptr(zc),
+                None if zc_act is zc else _L.ptr(zc_act), act_dt, z.shape[0], z.shape[1], _st())
+        return zc, zc_act
+
+    def _zero_masked(self, z, mask):
+        """where(mask == 0, 0, z) (legacy body nolbo.py:1544-1548): the latent_correct kernel with a zero prototype table and
+        zero epsilon.  Returns (float32, activation-dtype) copies."""
+        B, Lz = z.shape
+        zeros = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=self._device)
+        return self._latent_correct(z, mask, zeros(1, Lz), zeros(B, dtype=torch.int32), zeros(B, Lz))
 
     def _category_acc(self, z, cats, onehot, mask=None):
         B, Lz, C = z.shape[0], z.shape[1], cats.shape[0]
@@ -108,21 +163,14 @@ class _ModelnetBase(object):
 
     def _fit(self, inputs, eps, drop_mask, drop_rate):
         """One optimisation step (GradientTape + Adam.apply_gradients of the reference) through voxvae.train.Trainer."""
-        from voxvae import train as _T
-        if getattr(self, '_trainer', None) is None:
-            import torch.distributed as dist
-            world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
-            self._trainer = _T.Trainer(self._enc_eng, self._dec_eng, self._variational, self._learning_rate, world_size=world)
-        input_images, output_images = inputs
-        x, y = self._dev_pair(input_images, output_images)
+        x, y = self._dev_pair(*inputs)
         mask, scale = None, 1.0
         if self._dropout:      # reference nolbo.py:1423-1425: rate ~ U[0,1) per step, inverted dropout on z
             rate = float(np.random.rand()) if drop_rate is None else float(drop_rate)
-            Lz = self._latent_dim
             if drop_mask is None:
-                drop_mask = (np.random.rand(x.shape[0], Lz) >= rate).astype('float32')
+                drop_mask = (np.random.rand(x.shape[0], self._latent_dim) >= rate).astype('float32')
             mask, scale = self._dev(drop_mask), 1.0 / (1.0 - rate)
-        kl, stats, m = self._trainer.step(x, y, None if eps is None else self._dev(eps), mask, scale)
+        kl, stats, m = self._train_helper().step(x, y, None if eps is None else self._dev(eps), mask, scale)
         return kl, m
 
     # ---------------------------------------------------------------- public API (reference signatures)
@@ -132,52 +180,57 @@ class _ModelnetBase(object):
         the last five being 0 when missing_prob == 0.
         Legacy form still used by the reference's train scripts (train_modelnet_category_VAE.py:83-84, body kept as
         the commented block nolbo.py:1530-1555): inputs=(x, y) without category_vectors -> (pred, loss_shape, pr, rc)."""
-        if training:
-            return self._getEval_training_mode(inputs, category_vectors, missing_prob, _eps, _mask, _eps2)
         if len(inputs) == 2 or category_vectors is None:
-            return self._getEval_legacy(inputs, missing_prob, _eps, _mask)
+            return self._getEval_legacy(inputs, training, missing_prob, _eps, _mask)
         input_images, output_images, category_list = inputs
         from voxvae.hostio import PackedVoxels as _PV
-        if missing_prob == 0.0 and isinstance(input_images, (np.ndarray, _PV)) and isinstance(output_images, (np.ndarray, _PV)):
+        if not training and missing_prob == 0.0 and isinstance(input_images, (np.ndarray, _PV)) and isinstance(output_images, (np.ndarray, _PV)):
             out = self._getEval_host_chunked(input_images, output_images, category_list, category_vectors, _eps,
                                              lazy=getattr(self, '_lazy_host', False))
             if out is not None:
                 return out
         x, y = self._dev_pair(input_images, output_images)
-        onehot = self._dev(category_list)
-        cats = self._dev(category_vectors)
-        B, Lz, C = x.shape[0], self._latent_dim, cats.shape[0]
-        h1 = None
-        if missing_prob > 0:
-            z, z_act, _ = self._encode_latent(x, _eps)
-        else:
-            z, z_act, _, h1 = self._encode_decode_seed(x, _eps)
+        onehot, cats = self._dev(category_list), self._dev(category_vectors)
+        latent, decode = self._eval_hooks(training, seed=not missing_prob > 0)
+        twin = not training
+        z, z_act, _, h1 = latent(x, _eps)
+        z_act = z_act if twin else z                                                  # training: float32 to the decoder entry (_eval_hooks)
         mask = None
         if missing_prob > 0:
-            if _mask is None:   # reference nolbo.py:1475-1476, same RNG call
-                _mask = np.reshape(np.random.choice(2, B * Lz, p=[missing_prob, 1. - missing_prob]), [B, Lz]).astype('float32')
-            mask = self._dev(_mask)
-            zf = torch.empty_like(z)
-            zf_act = zf if self._act_dt == _L.VV_F32 else torch.empty(B, Lz, dtype=torch.bfloat16, device=self._device)
-            _L.call('vv_latent_mask_fill', _L.ptr(z), _L.ptr(mask), _L.ptr(cats), C, _L.ptr(zf),
-                    None if zf_act is zf else _L.ptr(zf_act), self._act_dt, B, Lz, _st())
-            z, z_act = zf, zf_act
-        _, acc = self._category_acc(z, cats, onehot)
-        pred, _, m = self._decode_metrics(z_act, y, h1)
+            mask = self._draw_mask(z.shape[0], missing_prob, _mask)                   # :1475-1476
+            z, z_act = self._mask_fill(z, mask, cats, twin)                           # :1477-1482
+        _, acc = self._category_acc(z, cats, onehot)                                  # :1489-1494
+        pred, _, m = decode(z_act, y, h1)                                             # :1496-1501
         self._z_category = DeviceArray(z)
-        res = (DeviceArray(pred), DeviceArray(m[0]), DeviceArray(m[1]), DeviceArray(m[2]), DeviceArray(acc[0]))
+        res = self._scored(pred, m, acc)
         if missing_prob == 0.0:
             return res + (0, 0, 0, 0, 0)
-        idx, _ = self._category_acc(z, cats, None, mask)                          # :1505-1506
-        eps2 = torch.randn(B, Lz, dtype=torch.float32, device=self._device) if _eps2 is None else self._dev(_eps2)
-        zc = torch.empty_like(z)
-        zc_act = zc if self._act_dt == _L.VV_F32 else torch.empty(B, Lz, dtype=torch.bfloat16, device=self._device)
-        _L.call('vv_latent_correct', _L.ptr(z), _L.ptr(mask), _L.ptr(cats), _L.ptr(idx), _L.ptr(eps2), _L.ptr(zc),
-                None if zc_act is zc else _L.ptr(zc_act), self._act_dt, B, Lz, _st())  # :1507-1510
-        _, acc_c = self._category_acc(zc, cats, onehot)                           # :1512-1518
-        pred_c, _, mc = self._decode_metrics(zc_act, y)                           # :1520-1527
+        idx, _ = self._category_acc(z, cats, None, mask)                              # :1505-1506
+        zc, zc_act = self._latent_correct(z, mask, cats, idx, self._draw_eps(z.shape[0], _eps2), twin)   # :1507-1510
+        _, acc_c = self._category_acc(zc, cats, onehot)                               # :1512-1518
+        pred_c, _, mc = decode(zc_act, y, None)                                       # :1520-1527
         self._z_category_corrected = DeviceArray(zc)
-        return res + (DeviceArray(pred_c), DeviceArray(mc[0]), DeviceArray(mc[1]), DeviceArray(mc[2]), DeviceArray(acc_c[0]))
+        return res + self._scored(pred_c, mc, acc_c)
+
+    @staticmethod
+    def _scored(pred, m, acc=None):
+        """(prediction, loss_shape, precision, recall[, category accuracy]) as the public methods return them."""
+        out = (DeviceArray(pred), DeviceArray(m[0]), DeviceArray(m[1]), DeviceArray(m[2]))
+        return out if acc is None else out + (DeviceArray(acc[0]),)
+
+    def _getEval_legacy(self, inputs, training, missing_prob, _eps, _mask):
+        """The 2-input form (commented body nolbo.py:1530-1555) -> (pred, loss_shape, pr, rc): the same two hooks, and with
+        missing_prob > 0 the masked latent entries become 0 (:1544-1548)."""
+        if training and self._enc_eng is None:
+            raise ValueError('nolboSingleObject_VAE.getEval takes (images, voxels, one-hot) and category_vectors')
+        x, y = self._dev_pair(inputs[0], inputs[1])
+        latent, decode = self._eval_hooks(training)
+        z, z_act, _, h1 = latent(x, _eps)
+        if missing_prob > 0:
+            zc, zc_act = self._zero_masked(z, self._draw_mask(z.shape[0], missing_prob, _mask))
+            z_act = zc if training else zc_act                                            # training: as in getEval (_eval_hooks)
+        pred, _, m = decode(z_act, y, h1)
+        return self._scored(pred, m)
 
     def _getEval_host_chunked(self, input_images, output_images, category_list, category_vectors, _eps, lazy=False):
         """getEval(missing_prob=0) on HOST arrays (the reference's calling convention, test_modelnet_VAE.py:114-130) as a
@@ -190,7 +243,7 @@ class _ModelnetBase(object):
         kernels and the returned HostPrediction waits for it on first access; ONE pass over the whole batch by default (the overlap
         comes from the NEXT batch, issued by the pipeline on another stream, and whole-batch kernels fill the chip)."""
         from voxvae import hostio as _H
-        if getattr(self, '_enc_eng', None) is None or input_images.ndim != 5:
+        if self._enc_eng is None or input_images.ndim != 5:
             return None                                  # the image -> 3D model: its inputs are images / head outputs, not voxel grids
         B = int(input_images.shape[0])
         # Two chunks pay when the download is the long pole (float32 probabilities: 33.6 MB at the PCIe rate = 0.60 ms beside 0.49 ms of
@@ -221,10 +274,7 @@ class _ModelnetBase(object):
             if getattr(self, '_io_streams', None) is None or len(self._io_streams) != nchunk:
                 self._io_streams = [torch.cuda.Stream(device=dev) for _ in range(nchunk)]
             io_streams = self._io_streams
-        Lz = self._latent_dim
-        eps = None
-        if self._variational:
-            eps = torch.randn(B, Lz, dtype=torch.float32, device=dev) if _eps is None else self._dev(_eps)
+        eps = self._draw_eps(B, _eps) if self._variational else None
         onehot, cats = self._dev(category_list), self._dev(category_vectors)
         self._enc_eng.ensure_packed()               # weight packing (first call / after a weight change) stays on the caller's stream
         self._dec_eng.ensure_packed()
@@ -270,102 +320,20 @@ class _ModelnetBase(object):
             self._trainer = _T.Trainer(self._enc_eng, self._dec_eng, self._variational, self._learning_rate, world_size=world)
         return self._trainer
 
-    def _getEval_training_mode(self, inputs, category_vectors, missing_prob, _eps, _mask, _eps2):
-        """getEval(training=True) (reference nolbo.py:1449, 1463, 1496: `self._encoder(x, training=training)`): the same
-        algebra with BatchNorm in training mode -- batch statistics, and the moving statistics move (momentum 0.99) -- and no
-        optimisation step.  Both decoder passes run in that mode, as in the reference."""
-        tr = self._train_helper()
-        if len(inputs) == 2 or category_vectors is None:
-            x, y = self._dev_pair(inputs[0], inputs[1])
-            zero = None
-            if missing_prob > 0:     # legacy body nolbo.py:1544-1548: masked entries become 0 (as in _getEval_legacy)
-                Bz, Lz = x.shape[0], self._latent_dim
-                if _mask is None:
-                    _mask = np.reshape(np.random.choice(2, Bz * Lz, p=[missing_prob, 1. - missing_prob]), [Bz, Lz]).astype('float32')
-                mk = self._dev(_mask)
-                zero = lambda z: self._zero_masked(z, mk)[0]
-            _, _, probs, _, m = tr.forward_training_mode(x, y, None if _eps is None else self._dev(_eps), z_fn=zero)
-            return DeviceArray(probs), DeviceArray(m[0]), DeviceArray(m[1]), DeviceArray(m[2])
-        input_images, output_images, category_list = inputs
-        x, y = self._dev_pair(input_images, output_images)
-        onehot = self._dev(category_list)
-        cats = self._dev(category_vectors)
-        B, Lz, C = x.shape[0], self._latent_dim, cats.shape[0]
-        mask = None
-        if missing_prob > 0:
-            if _mask is None:
-                _mask = np.reshape(np.random.choice(2, B * Lz, p=[missing_prob, 1. - missing_prob]), [B, Lz]).astype('float32')
-            mask = self._dev(_mask)
-
-        def fill(z):
-            if mask is None:
-                return z
-            zf = torch.empty_like(z)
-            _L.call('vv_latent_mask_fill', _L.ptr(z), _L.ptr(mask), _L.ptr(cats), C, _L.ptr(zf), None, _L.VV_F32, B, Lz, _st())
-            return zf
-
-        z, _, probs, _, m = tr.forward_training_mode(x, y, None if _eps is None else self._dev(_eps), z_fn=fill)
-        _, acc = self._category_acc(z, cats, onehot)
-        self._z_category = DeviceArray(z)
-        res = (DeviceArray(probs), DeviceArray(m[0]), DeviceArray(m[1]), DeviceArray(m[2]), DeviceArray(acc[0]))
-        if missing_prob == 0.0:
-            return res + (0, 0, 0, 0, 0)
-        idx, _ = self._category_acc(z, cats, None, mask)
-        eps2 = torch.randn(B, Lz, dtype=torch.float32, device=self._device) if _eps2 is None else self._dev(_eps2)
-        zc = torch.empty_like(z)
-        _L.call('vv_latent_correct', _L.ptr(z), _L.ptr(mask), _L.ptr(cats), _L.ptr(idx), _L.ptr(eps2), _L.ptr(zc), None, _L.VV_F32,
-                B, Lz, _st())
-        _, acc_c = self._category_acc(zc, cats, onehot)
-        probs_c, _, mc = tr.decoder_training_mode(zc, y)
-        self._z_category_corrected = DeviceArray(zc)
-        return res + (DeviceArray(probs_c), DeviceArray(mc[0]), DeviceArray(mc[1]), DeviceArray(mc[2]), DeviceArray(acc_c[0]))
-
-    def _zero_masked(self, z, mask):
-        """where(mask == 0, 0, z) (legacy body nolbo.py:1544-1548): the latent_correct kernel with a zero prototype table and
-        zero epsilon.  Returns (float32, activation-dtype) copies."""
-        B, Lz = z.shape
-        zeros = torch.zeros(1, Lz, dtype=torch.float32, device=self._device)
-        idx0 = torch.zeros(B, dtype=torch.int32, device=self._device)
-        e0 = torch.zeros(B, Lz, dtype=torch.float32, device=self._device)
-        zc = torch.empty_like(z)
-        zc_act = zc if self._act_dt == _L.VV_F32 else torch.empty(B, Lz, dtype=torch.bfloat16, device=self._device)
-        _L.call('vv_latent_correct', _L.ptr(z), _L.ptr(mask), _L.ptr(zeros), _L.ptr(idx0), _L.ptr(e0), _L.ptr(zc),
-                None if zc_act is zc else _L.ptr(zc_act), self._act_dt, B, Lz, _st())
-        return zc, zc_act
-
-    def _getEval_legacy(self, inputs, missing_prob, _eps, _mask):
-        input_images, output_images = inputs[0], inputs[1]
-        x, y = self._dev_pair(input_images, output_images)
-        z, z_act, _ = self._encode_latent(x, _eps)
-        if missing_prob > 0:   # commented body nolbo.py:1544-1548: masked entries become 0
-            B, Lz = z.shape
-            if _mask is None:
-                _mask = np.reshape(np.random.choice(2, B * Lz, p=[missing_prob, 1. - missing_prob]), [B, Lz]).astype('float32')
-            _, z_act = self._zero_masked(z, self._dev(_mask))
-        pred, _, m = self._decode_metrics(z_act, y)
-        return DeviceArray(pred), DeviceArray(m[0]), DeviceArray(m[1]), DeviceArray(m[2])
-
     def getLatent(self, inputs, *, _eps=None):
         """reference nolbo.py:1557-1566 (VAE: a SAMPLED z) / :1355-1358 (AE: the encoder output) -> numpy [B,L]."""
         z, _, _ = self._encode_latent(self._dev(inputs), _eps)
         return np.array(DeviceArray(z))
 
     # ---------------------------------------------------------------- sampled-mean reconstruction (an extension)
-    def _posterior_of(self, enc_out):
-        """(mean | logVar) [B,2L] -> (mean, clipped logVar) [B,L] through the class's own latent op (vv_reparam_kl_fwd's outputs;
-        nolbo.py:1417-1420)."""
-        Lz = self._latent_dim
-        if enc_out.dim() != 2 or enc_out.shape[1] != 2 * Lz:
-            raise ValueError('the encoder must emit [B, %d] (mean | logVar), got %s' % (2 * Lz, tuple(enc_out.shape)))
-        zero = torch.zeros(enc_out.shape[0], Lz, dtype=torch.float32, device=self._device)
-        _, _, _, mean, logvar = _E.reparam_kl(enc_out, zero, Lz, self._act_dt, want_stats=True)
-        return mean, logvar
-
     def _posterior(self, x):
-        """encoder -> (mean, clipped logVar) [B,L]; classes without a posterior (the autoencoder) raise ValueError."""
+        """encoder -> (mean, clipped logVar) [B,L] through the class's own latent op (vv_reparam_kl_fwd's outputs; nolbo.py:1417-1420);
+        classes without a posterior (the autoencoder) raise ValueError."""
         if not self._variational:
             raise ValueError('%s has no posterior to sample from (an autoencoder): getSampledEval needs a variational class' % type(self).__name__)
-        return self._posterior_of(self._enc_eng.forward(x))
+        enc_out = self._enc_out(x)
+        zero = torch.zeros(enc_out.shape[0], self._latent_dim, dtype=torch.float32, device=self._device)
+        return self._reparam(enc_out, zero, want_stats=True)[3:]
 
     def getSampledShape(self, mean, logvar, sampling_num=32, target=None, *, _eps=None, max_decode_batch=256):
         """The "anytime" reconstruction of the reference's nolbo_test.py:169-177 at latent level: `sampling_num` latents
@@ -398,7 +366,7 @@ class _ModelnetBase(object):
         if y is None:
             return DeviceArray(pred)
         m = _E.shape_metrics(stats[0] if len(stats) == 1 else torch.cat(stats))
-        return DeviceArray(pred), DeviceArray(m[0]), DeviceArray(m[1]), DeviceArray(m[2])
+        return self._scored(pred, m)
 
     def getSampledEval(self, inputs, sampling_num=32, *, _eps=None):
         """inputs = (x, y): the encoder runs once per object, `sampling_num` latents are drawn from its posterior (mean and the clipped
@@ -566,7 +534,7 @@ class nolboSingleObject_VAE(_ModelnetBase):
         print('build Models...')
         # ==============set decoder3D
         self._decoder = ae3D.decoder3D(structure=self._dec_str)
-        self._dec_eng = self._decoder._engine
+        self._enc_eng, self._dec_eng = None, self._decoder._engine      # no voxel encoder: the latent comes from the 2D encoder
         self._device = self._dec_eng.device
         self._act_dt = self._dec_eng.dt
         if self._encoder_backbone is None and self._backbone_style is not None:
@@ -590,61 +558,21 @@ class nolboSingleObject_VAE(_ModelnetBase):
         f = self._encoder_backbone(x, training=training) if self._encoder_head is not None else self._encoder_backbone(x)
         return self._encoder_head(f, training=training) if self._encoder_head is not None else f
 
-    def _encode_latent(self, x, eps=None, want_kl=False):
-        enc_out = self._dev(self._encoder_2d(x, training=False))
-        Lz = self._latent_dim
-        if enc_out.dim() != 2 or enc_out.shape[1] != 2 * Lz:
-            raise ValueError('the 2D encoder must emit [B, %d] (mean | logVar), got %s' % (2 * Lz, tuple(enc_out.shape)))
-        eps = torch.randn(enc_out.shape[0], Lz, dtype=torch.float32, device=self._device) if eps is None else self._dev(eps)
-        z, z_act, kl, _, _ = _E.reparam_kl(enc_out, eps, Lz, self._act_dt)
-        return z, z_act, kl
+    def _enc_out(self, x, training=False):
+        return self._dev(self._encoder_2d(x, training=training)).contiguous()
 
-    def _posterior(self, x):
-        return self._posterior_of(self._dev(self._encoder_2d(x, training=False)).contiguous())
+    def _latent_training_mode(self, x, eps=None):
+        """Reference nolbo.py:856-928 passes `training` to the backbone and the head (torch modules) as well as to the decoder."""
+        with torch.no_grad():
+            enc_out = self._enc_out(x, training=True)
+        return self._reparam(enc_out, eps, _L.VV_F32)[:3] + (None,)
 
-    def _encode_decode_seed(self, x, eps=None):
-        """No voxel encoder here (the latent comes from the 2D encoder / supplied head outputs): the split calls."""
-        z, z_act, kl = self._encode_latent(x, eps)
-        return z, z_act, kl, None
-
-    def _getEval_training_mode(self, inputs, category_vectors, missing_prob, _eps, _mask, _eps2):
-        """getEval(training=True) of the image -> 3D model (reference nolbo.py:856-928 passes `training` to the backbone, the head
-        and the decoder): the 2D encoder runs in training mode (torch modules), the decoder's BatchNorm normalises with batch
-        statistics and moves its moving statistics; no optimisation step."""
+    def _train_helper(self):
+        """Training-mode forwards need the decoder's half only: a trainer without gradient / optimiser state."""
         from voxvae import train as _T
-        if category_vectors is None or len(inputs) != 3:
-            raise ValueError('nolboSingleObject_VAE.getEval takes (images, voxels, one-hot) and category_vectors')
         if getattr(self, '_fwd_dec', None) is None:
             self._fwd_dec = _T.Trainer.forward_only(dec=self._dec_eng)
-        input_images, output_images, category_list = inputs
-        y, onehot, cats = self._dev(output_images), self._dev(category_list), self._dev(category_vectors)
-        with torch.no_grad():
-            enc_out = self._dev(self._encoder_2d(input_images, training=True))
-        B, Lz, C = enc_out.shape[0], self._latent_dim, cats.shape[0]
-        eps = torch.randn(B, Lz, dtype=torch.float32, device=self._device) if _eps is None else self._dev(_eps)
-        z, _, _, _, _ = _E.reparam_kl(enc_out.contiguous(), eps, Lz, _L.VV_F32)
-        mask = None
-        if missing_prob > 0:
-            if _mask is None:
-                _mask = np.reshape(np.random.choice(2, B * Lz, p=[missing_prob, 1. - missing_prob]), [B, Lz]).astype('float32')
-            mask = self._dev(_mask)
-            zf = torch.empty_like(z)
-            _L.call('vv_latent_mask_fill', _L.ptr(z), _L.ptr(mask), _L.ptr(cats), C, _L.ptr(zf), None, _L.VV_F32, B, Lz, _st())
-            z = zf
-        _, acc = self._category_acc(z, cats, onehot)
-        probs, _, m = self._fwd_dec.decoder_training_mode(z, y)
-        self._z_category = DeviceArray(z)
-        res = (DeviceArray(probs), DeviceArray(m[0]), DeviceArray(m[1]), DeviceArray(m[2]), DeviceArray(acc[0]))
-        if missing_prob == 0.0:
-            return res + (0, 0, 0, 0, 0)
-        idx, _ = self._category_acc(z, cats, None, mask)
-        eps2 = torch.randn(B, Lz, dtype=torch.float32, device=self._device) if _eps2 is None else self._dev(_eps2)
-        zc = torch.empty_like(z)
-        _L.call('vv_latent_correct', _L.ptr(z), _L.ptr(mask), _L.ptr(cats), _L.ptr(idx), _L.ptr(eps2), _L.ptr(zc), None, _L.VV_F32, B, Lz, _st())
-        _, acc_c = self._category_acc(zc, cats, onehot)
-        probs_c, _, mc = self._fwd_dec.decoder_training_mode(zc, y)
-        self._z_category_corrected = DeviceArray(zc)
-        return res + (DeviceArray(probs_c), DeviceArray(mc[0]), DeviceArray(mc[1]), DeviceArray(mc[2]), DeviceArray(acc_c[0]))
+        return self._fwd_dec
 
     def _dev(self, a):
         if callable(getattr(a, 'numpy', None)) and not isinstance(a, (torch.Tensor, DeviceArray)):
@@ -665,7 +593,7 @@ class nolboSingleObject_VAE(_ModelnetBase):
         trainable_2d = self._opt2d is not None
         enc_out = self._encoder_2d(input_images, training=True) if trainable_2d else self._dev(self._encoder_2d(input_images))
         B, Lz = enc_out.shape[0], self._latent_dim
-        eps = torch.randn(B, Lz, dtype=torch.float32, device=self._device) if _eps is None else self._dev(_eps)
+        eps = self._draw_eps(B, _eps)
         drop_mask, drop_scale = None, 1.0
         if self._dropout:
             rate, keep = _dropout if _dropout is not None else (float(np.random.rand()), None)
@@ -707,14 +635,6 @@ class nolboSingleObject_VAE(_ModelnetBase):
         self.loadEncoderBackbone(load_path)
         self.loadEncoderHead(load_path)
 
-    def saveModel(self, save_path):
-        self.saveEncoder(save_path=save_path)
-        self.saveDecoder(save_path=save_path)
-
-    def loadModel(self, load_path):
-        self.loadEncoder(load_path=load_path)
-        self.loadDecoder(load_path=load_path)
-
 
 class nolboSingleObject_modelnet_category_only(_ModelnetBase):
     """reference nolbo.py:1594-1787: the VAE with a learned class-conditional prior.  Encoder, decoder, losses and the
@@ -751,8 +671,7 @@ class nolboSingleObject_modelnet_category_only(_ModelnetBase):
             self._opt_prior = torch.optim.Adam(self._priornet_class.parameters(), lr=self._learning_rate, eps=1e-7)
         r = _rand or {}
         dev = self._device
-        eps = self._dev(r['eps']) if 'eps' in r else torch.randn(B, Lz, device=dev)
-        eps_p = self._dev(r['eps_prior']) if 'eps_prior' in r else torch.randn(B, Lz, device=dev)
+        eps, eps_p = self._draw_eps(B, r.get('eps')), self._draw_eps(B, r.get('eps_prior'))
         mix = bool(r['mix']) if 'mix' in r else not (np.random.rand() > 0.5)       # :1642: z itself with probability 1/2
         noise = None
         if mix:

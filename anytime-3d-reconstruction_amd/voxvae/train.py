@@ -309,8 +309,8 @@ class Trainer:
         return L.VV_BF16 if t.dtype == torch.bfloat16 else L.VV_F32
 
     def _cast(self, t):
-        """float32 tensor -> the activation dtype (a copy only in bf16 mode)."""
-        if self.dt == L.VV_F32:
+        """float32 tensor -> the activation dtype (a copy only in bf16 mode; a tensor already in that dtype is returned as it is)."""
+        if self.dt == L.VV_F32 or t.dtype == self.tdt:
             return t
         o = torch.empty(t.shape, dtype=self.tdt, device=self.dev)
         L.call('vv_convert', L.ptr(t), L.ptr(o), t.numel(), L.VV_F32, self.dt, _st())
@@ -562,25 +562,27 @@ class Trainer:
                 raise NotImplementedError('latent dropout for the AE class')
         return z, z_act, kl, eps
 
-    def forward_training_mode(self, x, y, eps=None, z_fn=None):
-        """The model called with training=True and NO optimisation step (getEval(training=True), reference nolbo.py:1449,
-        1463, 1496): BatchNorm normalises with the batch statistics and updates its moving statistics, nothing else changes.
-        z_fn(z float32 [B,L]) -> z may edit the latent before the decoder (missing-latent masking).
-        Returns (z, kl or None, probs, stats [B,4], metrics [4])."""
+    def latent_training_mode(self, x, eps=None):
+        """Encoder half of forward_training_mode -> (z float32 [B,L], z_act, kl or None).  BOTH engines are packed here (one _begin
+        for the whole forward: the pack launches keep their order); decoder_training_mode decodes the latent, edited or not.  Its
+        own _begin(dec) then finds the decoder packed and launches nothing: it only re-reads the switches."""
         self._begin(self.enc, self.dec)
         B = x.shape[0]
         enc_out, _ = self._encoder_forward(x, B)
         z, z_act, kl, _ = self._latent(enc_out, eps, None, 1.0, B)
-        if z_fn is not None:
-            z = z_fn(z)
-            z_act = self._cast(z)
-        fw = self._decoder_forward(z_act, y, B)
         self.enc.statistics_moved()
-        self.dec.statistics_moved()
-        return z, kl, fw['probs'], fw['stats'], fw['metrics']
+        return z, z_act, kl
+
+    def forward_training_mode(self, x, y, eps=None):
+        """The model called with training=True and NO optimisation step (getEval(training=True), reference nolbo.py:1449,
+        1463, 1496): BatchNorm normalises with the batch statistics and updates its moving statistics, nothing else changes.
+        The two halves in one call; getEval calls them itself (it edits the latent in between), so this one is kept for outside
+        callers and the engine-level call trace (tests/test_call_trace.py).  Returns (z, kl or None, probs, stats [B,4], metrics [4])."""
+        z, z_act, kl = self.latent_training_mode(x, eps)
+        return (z, kl) + self.decoder_training_mode(z_act, y)
 
     def decoder_training_mode(self, z, y):
-        """Decoder half of forward_training_mode for an edited latent (the corrected pass of getEval)."""
+        """Decoder half of forward_training_mode: z float32 [B,L] (cast here) or already in the activation dtype."""
         self._begin(self.dec)
         fw = self._decoder_forward(self._cast(z), y, z.shape[0])
         self.dec.statistics_moved()

@@ -205,8 +205,8 @@ def _store(traces):
 
 
 @functools.lru_cache(maxsize=None)
-def _golden():
-    with open(GOLDEN) as f:
+def _golden(path=GOLDEN):
+    with open(path) as f:
         g = json.load(f)
     return {name: [g['calls'][i] for i in t.split()] for name, t in g['traces'].items()}
 

@@ -273,6 +273,45 @@ def test_fit_step_with_latent_dropout_matches_autograd_oracle():
     assert worst['enc/conv4/kernel'] < 2e-3
 
 
+def _assert_ten_tuple_values(out, want, model, det=None):
+    """The 10-tuple of the missing-latent getEval against float64 values, at the tolerances the neighbouring tests use for this same
+    training-mode forward: probabilities 2e-5, loss_shape 2e-4 relative, precision / recall 1e-3, accuracies exact to 1e-6; with `det`,
+    _z_category / _z_category_corrected against det['z'] / det['z_corr'] at 2e-5 (tests/test_gpu_api.py's latent bound)."""
+    assert len(out) == 10 and len(want) == 10
+    for k in (0, 5):
+        err = float(np.abs(np.array(out[k]) - want[k].reshape(np.array(out[k]).shape)).max())
+        print('probabilities [%d]: max |d| %.3e' % (k, err))
+        assert err <= 2e-5
+    for k in (1, 6):
+        err = abs(float(out[k]) - float(want[k])) / abs(float(want[k]))
+        print('loss_shape [%d]: relative error %.3e' % (k, err))
+        assert err <= 2e-4
+    for k in (2, 3, 7, 8):
+        err = abs(float(out[k]) - float(want[k]))
+        print('precision / recall [%d]: |d| %.3e' % (k, err))
+        assert err < 1e-3
+    for k in (4, 9):
+        assert abs(float(out[k]) - float(want[k])) <= 1e-6, (k, float(out[k]), float(want[k]))
+    if det is not None:
+        for got, name in ((model._z_category, 'z'), (model._z_category_corrected, 'z_corr')):
+            err = float(np.abs(np.array(got) - det[name]).max())
+            print('%s: max |d| %.3e' % (name, err))
+            assert err <= 2e-5
+
+
+def _missing_latent_oracle(cfg, ep, dp, x, eps, var):
+    """getEval(training=True, missing_prob=0.5) of a _setup(16, 64, var, 6, ...) model in float64: (one-hot, prototypes, mask, eps2)
+    and the oracle's 10-tuple and details."""
+    from oracle import numpy_oracle as no
+    from voxvae import synthetic as syn
+    oh, cats = syn.make_onehot(6, 40), syn.make_category_vectors(40, 64)
+    mask = (np.random.default_rng(1).random((6, 64)) >= 0.5).astype(np.float32)
+    eps2 = syn.make_eps(6, 64, seed=5)
+    want, det = no.vae_get_eval(cfg, ep, dp, (x, x, oh), cats, eps, training=True, missing_prob=0.5, mask=mask, eps2=eps2,
+                                variational=var, details=True)
+    return (oh, cats, mask, eps2), want, det
+
+
 def test_getEval_training_true_uses_batch_statistics_and_moves_the_moving_ones():
     """getEval(training=True) (reference nolbo.py:1449, 1463, 1496): BatchNorm in training mode, no optimisation step.
     Predictions / loss / precision / recall against the training oracle's forward, the moving statistics against its
@@ -302,6 +341,45 @@ def test_getEval_training_true_uses_batch_statistics_and_moves_the_moving_ones()
     out3 = model.getEval(inputs=(x, x, oh), category_vectors=cats, training=True, missing_prob=0.5, _eps=eps, _mask=mask,
                          _eps2=syn.make_eps(6, 64, seed=5))
     assert len(out3) == 10 and all(np.isfinite(float(v)) for v in out3[1:5] + out3[6:10])
+    # ... to the oracle's values: batch statistics rule, so the moving statistics the two calls above moved do not enter
+    _, want, det = _missing_latent_oracle(cfg, ep, dp, x, eps, True)
+    _assert_ten_tuple_values(out3, want, model, det)
+
+
+def test_getEval_training_true_missing_latent_matches_the_oracle_autoencoder():
+    """The same check for the autoencoder class (reference nolbo.py:1260-1332 with training=True): all ten outputs and both latents."""
+    cfg, ep, dp, model, x, eps = _setup(16, 64, False, 6, seed=2)
+    (oh, cats, mask, eps2), want, det = _missing_latent_oracle(cfg, ep, dp, x, eps, False)
+    out = model.getEval(inputs=(x, x, oh), category_vectors=cats, training=True, missing_prob=0.5, _mask=mask, _eps2=eps2)
+    torch.cuda.synchronize()
+    _assert_ten_tuple_values(out, want, model, det)
+
+
+@pytest.mark.parametrize('training', [False, True])
+def test_getEval_uninjected_draws_are_the_documented_ones(training):
+    """getEval without injected draws makes the reference's RNG calls in the reference's order per generator: torch.randn for the
+    sampling epsilon (nolbo.py:1470), np.random.choice for the mask (:1475), torch.randn for the prior epsilon (:1508).  Drawing them by
+    hand after the same seeds and injecting them gives the same ten outputs bit for bit."""
+    from voxvae import synthetic as syn
+    B, Lz = 6, 64
+    cfg, ep, dp, model, x, _ = _setup(16, Lz, True, B, seed=2)
+    oh, cats = syn.make_onehot(B, 40), syn.make_category_vectors(40, Lz)
+    p = 0.5
+
+    def seed():
+        np.random.seed(11)
+        torch.manual_seed(11)
+
+    seed()
+    a = model.getEval(inputs=(x, x, oh), category_vectors=cats, training=training, missing_prob=p)
+    seed()
+    e = torch.randn(B, Lz, dtype=torch.float32, device=DEV)
+    mask = np.reshape(np.random.choice(2, B * Lz, p=[p, 1. - p]), [B, Lz]).astype('float32')
+    e2 = torch.randn(B, Lz, dtype=torch.float32, device=DEV)
+    b = model.getEval(inputs=(x, x, oh), category_vectors=cats, training=training, missing_prob=p, _eps=e, _mask=mask, _eps2=e2)
+    assert len(a) == 10 and len(b) == 10
+    for k in range(10):
+        np.testing.assert_array_equal(np.array(a[k]), np.array(b[k]), err_msg='output %d' % k)
 
 
 def test_eval_after_training_mode_forward_uses_the_moved_statistics():
@@ -615,6 +693,18 @@ def test_image_to_3d_model_getEval_training_true():
     o2 = m.getEval(inputs=(head, x, oh), category_vectors=cats, training=True, missing_prob=0.5, _eps=eps, _mask=mask, _eps2=syn.make_eps(B, Lz, seed=5))
     assert len(o2) == 10 and all(np.isfinite(float(v)) for v in o2[1:5] + o2[6:10])
     assert np.abs(np.array(o2[0]) - np.array(o2[5])).max() > 1e-3
+    # ... to the values composed from the oracle's primitives (nolbo.py:856-928 with training=True)
+    from oracle import numpy_oracle as no
+    eps2, m64, c64, y64 = syn.make_eps(B, Lz, seed=5).astype(np.float64), mask.astype(np.float64), cats.astype(np.float64), x.astype(np.float64)
+    mu, lv = no.split_mean_logvar(head.astype(np.float64), Lz)
+    z = no.latent_mask_fill(no.sampling(mu, lv, eps), m64, c64)
+    acc = no.category_accuracy(no.nearest_category(z, c64), oh)
+    _, probs = no.decoder3D_forward(cfgv['decoder'], dp, z, training=True)
+    z_corr = no.latent_correct(z, m64, c64, no.nearest_category(z, c64, m64), eps2)
+    acc_c = no.category_accuracy(no.nearest_category(z_corr, c64), oh)
+    _, probs_c = no.decoder3D_forward(cfgv['decoder'], dp, z_corr, training=True)
+    want = (probs,) + no._shape_metrics(probs, y64)[4:] + (acc, probs_c) + no._shape_metrics(probs_c, y64)[4:] + (acc_c,)
+    _assert_ten_tuple_values(o2, want, m, {'z': z, 'z_corr': z_corr})
 
 
 # ============================================================================================ training past the first step
