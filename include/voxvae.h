@@ -14,6 +14,11 @@
  *     are always float32.
  *   - functions return 0 (VV_OK) or a negative vv_status; they never throw, never allocate, never
  *     synchronise; scratch comes from the caller (`*_workspace_bytes`).  No global state: thread-safe per stream.
+ *   - memory discipline: an entry reads and writes only inside the tensors it was given.  A workspace is write-before-read
+ *     (whatever it held before the call does not matter; vv_convT3d_final_bce_metrics_fwd is a complete forward too,
+ *     alone or behind vv_convT3d_final_bce_fwd on the same workspace); an entry touches no more than its
+ *     `*_workspace_bytes` query says, and a `workspace_bytes` argument beyond that minimum changes nothing (one
+ *     workspace may serve every layer of a stream).
  */
 #ifndef VOXVAE_H
 #define VOXVAE_H

@@ -308,6 +308,14 @@ def test_conv3d_first(L, dtname, B, D, act=1):
         _check(y, ref, 'bf16', 'conv3d_first', pre)
 
 
+@pytest.mark.parametrize('B,D', [(1, 32), (7, 32)])
+def test_conv3d_first_gather_form_at_plane_sizes(L, B, D, monkeypatch):
+    """VV_FIRSTCONV_GATHER: the gather form on a grid the plane form takes by default, against the oracle at a small batch (the full-batch
+    cross-form test holds it to the plane form only at B = 256); B = 7 leaves a ragged last workgroup."""
+    monkeypatch.setenv('VV_FIRSTCONV_GATHER', '1')
+    test_conv3d_first(L, 'bf16', B, D)
+
+
 @pytest.mark.parametrize('dtname', ['f32', 'bf16'])
 @pytest.mark.parametrize('B,side,form', [(2, 16, 'box'), (3, 4, 'box'), (1, 8, 'box'), (2, 16, 'sweep'), (3, 8, 'sweep'), (1, 32, 'sweep'),
                                          (2, 16, 'sweepp'), (3, 8, 'sweepp')])
