@@ -102,6 +102,9 @@ SIGNATURES = {
     'vv_pose_ray_host': (_i, [_vp, ctypes.c_double, ctypes.c_double, _vp]),
     'vv_pose_ray_rotation_host': (_i, [_vp, _vp]),
     'vv_pose_box_projection_host': (_i, [_vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp]),
+    'vv_detect_decode': (_i, [_vp] + [_i] * 7 + [_f, _f, _i] + [_vp] * 9 + [_vp]),
+    'vv_detect_decode_host': (_i, [_vp] + [_i] * 7 + [_f, _f, _i] + [_vp] * 9),
+    'vv_detect_activation_host': (_i, [_vp, _vp, _l, _i]),
     'vv_latent_mask_fill':(_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     'vv_nearest_category': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     'vv_latent_correct': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

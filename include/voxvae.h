@@ -425,6 +425,47 @@ int vv_pose_box_projection_host(const double *proj, const double *rotation, cons
                                 double *corners);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Detector head -> selected detections (detect_decode.hip, detect_decode.h): nolbo_test.getPred of src/module/nolbo_test.py:81-153 with
+ * its _encOutPartitioning (:214-255) and function.nonMaximumSuppresion (src/module/function.py:117-150), for `batch` independent frames
+ * (the reference does frame 0 only).  All arithmetic is float32 in the reference's operation order and with its roundings under numpy 2.
+ *   head        float32, batch frames of grid_row x grid_col cells with channels = predictor_num * W values each, W = 1 + 4 + 3 + 2 Z + 9
+ *               (Z = z_dim; the reference: 5 predictors, Z = 16, 245 channels).  layout 0: [batch][row][col][channel] (channels
+ *               innermost); layout 1: [batch][channel][row][col] (planes: what the torch head holds before its final permute).  Any other
+ *               layout, or channels != predictor_num * W: VV_ERR_SHAPE.
+ *               Per predictor, in this order: objectness 1 (sigmoid) | bbox2D 4 = (h, w, x, y): exp, exp, sigmoid, sigmoid | bbox3D 3
+ *               (relu) | inst_mean Z | inst_log_var Z | sin 3 (tanh) | cos 3 (tanh) | rad_log_var 3.  exp, sigmoid and tanh are the
+ *               header's own (fmaf polynomials, no library call): exp overflows to +inf above 88.72283 as numpy's does and returns 0
+ *               below -87.3, sigmoid returns 0 below -87; a NaN stays a NaN.
+ *   limits      batch >= 1; 1 <= predictor_num <= 16; 1 <= z_dim <= 64; N = grid_row * grid_col * (top_1 ? 1 : predictor_num) <= 4096
+ *               candidate slots per frame.  Anything else: VV_ERR_SHAPE.
+ *   candidates  cells in row-major order; inside a cell the predictors in descending objectness, equal values the lower predictor first.
+ *               A predictor is a candidate when objectness > obj_thresh (strict; a NaN never is).  top_1 != 0: only the cell's first
+ *               predictor in that order can be one.
+ *   box         (col_min, row_min, col_max, row_max): t = f32(f32(row) + y), q = f32(t / grid_row) (correctly rounded),
+ *               row_min = f32(q - f32(h / 2)), row_max = f32(q + f32(h / 2)); columns likewise with x, w, grid_col.
+ *   NMS         greedy: candidates in descending objectness, equal values the HIGHER candidate index first (a stable ascending sort read
+ *               from its end; numpy's argsort gives no rule).  A pick suppresses every live candidate with IoU > iou_thresh (strict; a
+ *               NaN IoU -- 0/0, inf/inf -- suppresses nothing): area = (rMax - rMin) * (cMax - cMin), inter = max(0, .) * max(0, .),
+ *               union = f32(area_i + area_j) - inter, IoU = inter / union, max / min returning NaN for a NaN operand as numpy's do.
+ *   outputs     per frame b, rows in PICK order, row r of frame b at [b * N + r]:  count int32 [batch];  index int32 [batch][N] = cell *
+ *               predictor_num + predictor;  bbox2d float32 [batch][N][5] = (col_min, row_min, col_max, row_max, objectness) -- the row
+ *               vv_object_pose takes;  bbox3d float32 [batch][N][3] = (field 1, field 0, field 2) as the reference swaps them;
+ *               inst_mean, inst_log_var float32 [batch][N][Z];  sin_aei, cos_aei, rad_log_var float32 [batch][N][3].  Rows at or past
+ *               count[b] are not written.
+ * vv_detect_decode: ONE launch on the hipStream_t `hip_stream`, a 256-thread workgroup per frame, candidates in LDS (up to 135232 bytes), no workspace;
+ * ballots and population counts, a counting rank and a scan with one barrier per pick: no atomics, no sort, the same bits on every run.
+ * vv_detect_decode_host: the same code compiled for the CPU, every pointer a host pointer, no stream.  The two agree bit for bit.
+ * vv_detect_activation_host: the header's exp (which 0), sigmoid (1) or tanh (2) of n float32 values, on the host.
+ * Pointers need the alignment of their element type and no more. */
+int vv_detect_decode(const float *head, int layout, int batch, int grid_row, int grid_col, int predictor_num, int z_dim, int channels,
+                     float obj_thresh, float iou_thresh, int top_1, int *count, int *index, float *bbox2d, float *bbox3d,
+                     float *inst_mean, float *inst_log_var, float *sin_aei, float *cos_aei, float *rad_log_var, void *hip_stream);
+int vv_detect_decode_host(const float *head, int layout, int batch, int grid_row, int grid_col, int predictor_num, int z_dim, int channels,
+                          float obj_thresh, float iou_thresh, int top_1, int *count, int *index, float *bbox2d, float *bbox3d,
+                          float *inst_mean, float *inst_log_var, float *sin_aei, float *cos_aei, float *rad_log_var);
+int vv_detect_activation_host(const float *x, float *y, long n, int which);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Training path (nolboSingleObject_modelnet_category_{VAE,AE}.fit, nolbo.py:1411-1447 / 1230-1258).  float32.
  * Data gradients reuse the forward kernels: d(Conv3D k4 s2)/d(input) = vv_convT3d_k4s2_fwd with the SAME Keras
  * kernel array packed by vv_pack_convT_k4s2 (read as [4,4,4,Cout_T = Cin, Cin_T = Cout]); d(Conv3DTranspose k4 s2)/
