@@ -1,6 +1,7 @@
 """2D image encoders of the image -> 3D models, mirror of the reference's src/net_core/darknet.py.
 
-Outside the voxel hot path: stock PyTorch ops, no hand-written kernels.  Same builder
+Outside the voxel hot path: stock PyTorch ops by default; `engine='hip'` (or voxvae.set_image_engine('hip'))
+runs the inference form on the HIP 2D convolution instead (voxvae/conv2d.py, csrc/conv2d.hip).  Same builder
 names and arguments as the reference -- `Darknet19(name, activation)` (darknet.py:96-135) and
 `head2D(name, input_shape, output_dim, filter_num_list, filter_size_list, last_pooling, activation)`
 (darknet.py:152-173) -- returning callables `model(x, training=False)` over channels-last images [B,H,W,3] with the
@@ -45,23 +46,41 @@ class _ConvBNAct(nn.Module):
 class _Keras2D(nn.Module):
     """Channels-last in / out, `model(x, training=...)` call form, and the handful of Keras attributes the callers use."""
 
-    def __init__(self, name, device=None):
+    def __init__(self, name, device=None, engine=None):
         super().__init__()
         self.name = name
         self._device = torch.device(device if device is not None else ('cuda:0' if torch.cuda.is_available() else 'cpu'))
+        import voxvae
+        self._engine = voxvae.image_engine() if engine is None else engine
+        if self._engine not in ('torch', 'hip'):
+            raise ValueError(self._engine)
+        self._chain = None
 
     def _finish(self):
         self.to(self._device)
         self.eval()
+        if self._engine == 'hip':
+            # inference calls run csrc/conv2d.hip (voxvae.conv2d.Conv2dChain); this module keeps the parameters and the training form.
+            # No GPU: VoxVaeError, as for the 3D builders -- no fallback to the torch ops.
+            from voxvae.conv2d import Conv2dChain
+            self._chain = Conv2dChain(self)
         return self
 
     def body(self, x):
         raise NotImplementedError
 
+    def _hip_forward(self, x):
+        """[B,R,C,Cin] -> the chain's float32 channels-last output, pooled as the module's forward pools it."""
+        return self._chain(x)
+
     def __call__(self, x, training=False):
         if not torch.is_tensor(x):
             x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
         x = x.to(self._device, torch.float32)
+        if self._chain is not None and not training:
+            self.train(False)
+            with torch.no_grad():
+                return self._hip_forward(x)
         self.train(bool(training))
         with torch.set_grad_enabled(bool(training)):
             return nn.Module.__call__(self, x)
@@ -91,8 +110,8 @@ class _Darknet19(_Keras2D):
     _PLAN = [(32, 3), 'M', (64, 3), 'M', (128, 3), (64, 1), (128, 3), 'M', (256, 3), (128, 1), (256, 3), 'M',
              (512, 3), (256, 1), (512, 3), (256, 1), (512, 3), 'M', (1024, 3), (512, 1), (1024, 3), (512, 1), (1024, 3)]
 
-    def __init__(self, name=None, activation='elu', device=None):
-        super().__init__(name, device)
+    def __init__(self, name=None, activation='elu', device=None, engine=None):
+        super().__init__(name, device, engine)
         layers, cin = [], 3
         for item in self._PLAN:
             if item == 'M':
@@ -110,8 +129,8 @@ class _Darknet19(_Keras2D):
 
 class _Head2D(_Keras2D):
     def __init__(self, name, input_shape, output_dim, filter_num_list, filter_size_list, last_pooling=None, activation='elu',
-                 device=None):
-        super().__init__(name, device)
+                 device=None, engine=None):
+        super().__init__(name, device, engine)
         cin, layers = int(input_shape[-1]), []
         for c, k in zip(filter_num_list, filter_size_list):
             layers.append(_ConvBNAct(cin, c, k, activation, l2=0.0005))
@@ -132,16 +151,26 @@ class _Head2D(_Keras2D):
             return x.mean(dim=(2, 3))
         return x.permute(0, 2, 3, 1)
 
+    def _hip_forward(self, x):
+        y = self._chain(x)                                  # float32 [B,R,C,output_dim]
+        if self.last_pooling == 'max':
+            from voxvae.conv2d import max_over_positions
+            return max_over_positions(y)
+        if self.last_pooling == 'average':
+            return y.mean(dim=(1, 2))                       # a torch reduction on the float32 head output (include/voxvae.h says so)
+        return y
 
-def Darknet19(name=None, activation='elu', device=None):
+
+def Darknet19(name=None, activation='elu', device=None, engine=None):
+    """engine: 'torch' | 'hip' | None = voxvae.image_engine() now.  'hip' runs calls with training=False on csrc/conv2d.hip."""
     print('Darknet19', name)
-    m = _Darknet19(name=name, activation=activation, device=device)
+    m = _Darknet19(name=name, activation=activation, device=device, engine=engine)
     print('end Darknet19')
     return m
 
 
-def head2D(name, input_shape, output_dim, filter_num_list, filter_size_list, last_pooling=None, activation='elu', device=None):
+def head2D(name, input_shape, output_dim, filter_num_list, filter_size_list, last_pooling=None, activation='elu', device=None, engine=None):
     print('head start')
-    m = _Head2D(name, input_shape, output_dim, filter_num_list, filter_size_list, last_pooling, activation, device)
+    m = _Head2D(name, input_shape, output_dim, filter_num_list, filter_size_list, last_pooling, activation, device, engine)
     print('end head2D')
     return m

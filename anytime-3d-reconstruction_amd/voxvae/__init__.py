@@ -8,7 +8,7 @@
 import os
 
 _DEFAULTS = {'dtype': os.environ.get('VOXVAE_DTYPE', 'f32'), 'device': os.environ.get('VOXVAE_DEVICE', 'cuda:0'),
-             'fp8_policy': os.environ.get('VV_FP8_POLICY', 'mid')}
+             'fp8_policy': os.environ.get('VV_FP8_POLICY', 'mid'), 'image_engine': os.environ.get('VOXVAE_IMAGE_ENGINE', 'torch')}
 
 
 def set_default_dtype(dtype):
@@ -41,6 +41,19 @@ def set_fp8_policy(policy):
 
 def fp8_policy():
     return _DEFAULTS['fp8_policy']
+
+
+def set_image_engine(engine):
+    """What runs the inference form of the image encoder (src.net_core.darknet: Darknet19, head2D) in modules built afterwards:
+    'torch' (default: the stock PyTorch ops, as before) or 'hip' (voxvae.conv2d on csrc/conv2d.hip, in default_dtype(); training-mode
+    calls stay on the torch modules either way).  Environment: VOXVAE_IMAGE_ENGINE."""
+    if engine not in ('torch', 'hip'):
+        raise ValueError(engine)
+    _DEFAULTS['image_engine'] = engine
+
+
+def image_engine():
+    return _DEFAULTS['image_engine']
 
 
 def set_default_device(device):

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(PKG, 'lib', 'libvoxvae.so')
 HOOKS_LIB_PATH = os.path.join(PKG, 'lib', 'libvoxvae_hooks.so')
 HOOK_VARS = ('VV_CD_SHAPE', 'VV_CDH_STAGGER', 'VV_CDH_ABL', 'VV_DIRECT_MT', 'VV_LT_KSLICE', 'VV_SPLIT_TARGET', 'VV_SPLIT_MINCHUNKS', 'VV_NO_KHALVES', 'VV_POSMAJOR_CONV_SIDE',
              'VV_POSMAJOR_CONVT_SIDE', 'VV_STAGES', 'VV_NO_FIRSTCONV', 'VV_WGRAD_F32', 'VV_PG_TARGET', 'VV_CTW_PS', 'VV_CTW_SHAPE',
-             'VV_NO_WGRAD_PHASE', 'VV_BN_NB', 'VV_BN_SWEEP', 'VV_FINAL_BCE', 'VV_FIRSTCONV_GATHER', 'VV_FIRSTCONV_WGS', 'VV_FIRSTCONV_NOCHAIN', 'VV_CHUNK_SAMPLES')
+             'VV_NO_WGRAD_PHASE', 'VV_BN_NB', 'VV_BN_SWEEP', 'VV_FINAL_BCE', 'VV_FIRSTCONV_GATHER', 'VV_FIRSTCONV_WGS', 'VV_FIRSTCONV_NOCHAIN', 'VV_CHUNK_SAMPLES', 'VV_C2_SPLITS')
 
 VV_F32, VV_BF16, VV_FP8 = 0, 1, 2
 ACT = {None: 0, 'None': 0, 'linear': 0, 'elu': 1, 'relu': 2, 'lrelu': 3}
@@ -105,6 +105,13 @@ SIGNATURES = {
     'vv_detect_decode': (_i, [_vp] + [_i] * 7 + [_f, _f, _i] + [_vp] * 9 + [_vp]),
     'vv_detect_decode_host': (_i, [_vp] + [_i] * 7 + [_f, _f, _i] + [_vp] * 9),
     'vv_detect_activation_host': (_i, [_vp, _vp, _l, _i]),
+    'vv_conv2d_packed_bytes': (_sz, [_i, _i, _i, _i]),
+    'vv_pack_conv2d': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    'vv_conv2d_supported': (_i, [_i] * 5),
+    'vv_conv2d_splits': (_i, [_i] * 6),
+    'vv_conv2d_workspace_bytes': (_sz, [_i] * 7),
+    'vv_conv2d_fwd': (_i, [_vp] * 5 + [_i] * 7 + [_f, _i, _i, _vp, _sz, _vp]),
+    'vv_maxpool2d_same_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'vv_latent_mask_fill':(_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     'vv_nearest_category': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     'vv_latent_correct': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

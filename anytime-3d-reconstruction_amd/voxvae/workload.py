@@ -38,3 +38,34 @@ def layer_macs(config):
 def flops_per_reconstruction(config):
     lm = layer_macs(config)
     return 2 * sum(v for _, v, _ in lm), 2 * sum(d for _, _, d in lm)
+
+
+# ---- the image encoder (src/net_core/darknet.py): Conv2D k in {1, 3}, stride 1, SAME; MaxPool2D(2, 2, 'same') halves with ceil
+DARKNET19_PLAN = [(32, 3), 'M', (64, 3), 'M', (128, 3), (64, 1), (128, 3), 'M', (256, 3), (128, 1), (256, 3), 'M',
+                  (512, 3), (256, 1), (512, 3), (256, 1), (512, 3), 'M', (1024, 3), (512, 1), (1024, 3), (512, 1), (1024, 3)]
+NOLBO_HEAD = ([1024, 1024, 1024], [3, 3, 3], 245)      # nolbo_test's head: filter_num_list, filter_size_list, output_dim
+
+
+def _axis_pairs_2d(n, k):
+    """(output, tap) pairs per axis of a k s1 SAME conv on n cells."""
+    return sum(1 for o in range(n) for t in range(k) if 0 <= o - k // 2 + t < n)
+
+
+def image_encoder_macs(rows, cols, head=NOLBO_HEAD, plan=None):
+    """-> list of (layer name, valid MACs per image, dense MACs per image) for Darknet19 on a rows x cols image followed by a head
+    (filter_num_list, filter_size_list, output_dim), or by none (head=None).  Names: B1.. backbone convolutions, H1.. head, HL its last 1x1."""
+    out, cin, n = [], 3, 0
+    for item in (DARKNET19_PLAN if plan is None else plan):
+        if item == 'M':
+            rows, cols = (rows + 1) // 2, (cols + 1) // 2
+            continue
+        c, k = item
+        n += 1
+        out.append(('B%d' % n, _axis_pairs_2d(rows, k) * _axis_pairs_2d(cols, k) * cin * c, rows * cols * k * k * cin * c))
+        cin = c
+    if head is not None:
+        for i, (c, k) in enumerate(zip(head[0], head[1])):
+            out.append(('H%d' % (i + 1), _axis_pairs_2d(rows, k) * _axis_pairs_2d(cols, k) * cin * c, rows * cols * k * k * cin * c))
+            cin = c
+        out.append(('HL', rows * cols * cin * head[2], rows * cols * cin * head[2]))
+    return out

@@ -466,6 +466,44 @@ int vv_detect_decode_host(const float *head, int layout, int batch, int grid_row
 int vv_detect_activation_host(const float *x, float *y, long n, int which);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * The image encoder: Darknet19 and head2D (src/net_core/darknet.py:83-94 Darknet19Conv, :96-133 the backbone, :135-168 convHead /
+ * head2D) as channels-last 2D layers.  Here grids are NOT cubic and NOT powers of two: x [B,R,C,Cin], any batch, rows, cols >= 1.
+ *
+ *   y[b,r,c,co] = act(scale[co] * sum_{tr,tc,ci} x[b, r+tr-p, c+tc-p, ci] * w[tr,tc,ci,co] + shift[co]),   p = ksize / 2
+ *
+ * Conv2D(ksize in {1, 3}, strides 1, 'same', no bias) -> BatchNormalization folded by vv_fold_bn (Keras epsilon 1e-3) -> activation;
+ * taps outside the image contribute zero.  An implicit GEMM with rows m = (b R + r) C + c, K = ksize^2 Cin, N = Cout on MFMA with f32
+ * accumulation: dtype VV_BF16 = v_mfma_f32_32x32x16_bf16, VV_F32 = v_mfma_f32_32x32x2_f32 (the exact-f32 parity mode).  x and w_packed
+ * have `dtype`, y has `out_dtype` (VV_BF16 or VV_F32, chosen separately: the head's last convolution stores f32 from bf16 operands);
+ * scale / shift are float32 [Cout] and may be NULL (identity).  One rounding: the f32 accumulator goes through the f32 fold and the
+ * activation and is rounded once to out_dtype.
+ *   cin      3 or a multiple of 32.  cin == 3 is the IMAGE: x is float32 [B,R,C,3] whatever `dtype` says, and is rounded to `dtype`
+ *            as it is read.
+ *   cout     any value >= 1 (the packed image is padded to a multiple of 64 channels, the stores are masked).
+ *   act      VV_ACT_*; VV_ACT_LRELU uses `alpha` as its slope (darknet.py:87-88 uses 0.1; the 3D layers' entries keep their 0.3).
+ *   limits   every tensor at most 2^31 - 1 elements, else VV_ERR_SHAPE (cut the batch); so is every other shape above not taken.
+ *            All of it is decided before any launch.
+ *   small M  K is cut into vv_conv2d_splits(...) shares when the tiles alone would not fill the device; each share writes a float32
+ *            slab into the workspace and one more launch sums them in share order (no atomics: the same bits on every run).
+ *            1 share = one launch, no workspace.  vv_conv2d_workspace_bytes is the minimum; more changes nothing.
+ * vv_pack_conv2d: Keras kernel [k,k,cin,cout] float32 -> [ceil(k*k*cin/32)][ceil(cout/64)*64][32] of `dtype`, zero padded
+ *            (vv_conv2d_packed_bytes bytes; device to device).
+ * vv_maxpool2d_same_fwd: MaxPool2D(2, 2, 'same') (darknet.py:100-124): y [B,ceil(R/2),ceil(C/2),channels], ceil mode -- for an odd
+ *            size the last window is one wide (padding only at the end).  Exact in either dtype.
+ * head2D's last_pooling (darknet.py:165-168): 'max' is vv_max_over_positions on the float32 head output; 'average' has no entry
+ *            here and stays a reduction of the caller on that float32 output.
+ * The stream parameter is a hipStream_t passed as void*, like every `stream` above.  x, w_packed, y and the workspace are 16-byte aligned. */
+size_t vv_conv2d_packed_bytes(int ksize, int cin, int cout, int dtype);
+int vv_pack_conv2d(const float *w_keras, void *packed, int ksize, int cin, int cout, int dtype, void *hip_stream);
+int vv_conv2d_supported(int ksize, int cin, int cout, int dtype, int out_dtype);
+int vv_conv2d_splits(int batch, int rows, int cols, int ksize, int cin, int cout);
+size_t vv_conv2d_workspace_bytes(int batch, int rows, int cols, int ksize, int cin, int cout, int dtype);
+int vv_conv2d_fwd(const void *x, const void *w_packed, const float *scale, const float *shift, void *y, int batch, int rows, int cols,
+                  int cin, int cout, int ksize, int act, float alpha, int dtype, int out_dtype, void *workspace, size_t workspace_bytes,
+                  void *hip_stream);
+int vv_maxpool2d_same_fwd(const void *x, void *y, int batch, int rows, int cols, int channels, int dtype, void *hip_stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Training path (nolboSingleObject_modelnet_category_{VAE,AE}.fit, nolbo.py:1411-1447 / 1230-1258).  float32.
  * Data gradients reuse the forward kernels: d(Conv3D k4 s2)/d(input) = vv_convT3d_k4s2_fwd with the SAME Keras
  * kernel array packed by vv_pack_convT_k4s2 (read as [4,4,4,Cout_T = Cin, Cin_T = Cout]); d(Conv3DTranspose k4 s2)/
