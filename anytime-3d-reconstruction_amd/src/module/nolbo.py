@@ -725,3 +725,240 @@ class nolboSingleObject_modelnet_category_only(_ModelnetBase):
         self.loadEncoder(load_path=load_path)
         self.loadDecoder(load_path=load_path)
         self.loadPriorCategory(load_path=load_path)
+
+
+class nolboSingleObject(nolboSingleObject_VAE):
+    """The reference's multi-modal model, nolbo.py:49-324: an image encoder that emits a category latent and an instance latent
+    ([mean_c | logVar_c | mean_i | logVar_i]), a learned prior network for each, and missing-modality correction of the category
+    half against the category prior.  Structure keys as the reference's: encoder_backbone (z_category_dim, z_inst_dim), encoder_head,
+    decoder, prior_class, prior_inst.  The image encoder and the decoder are nolboSingleObject_VAE's (either image engine, the HIP
+    decoder engine); everything between the head output and the decoder input is ONE vv_mm_latent_eval (csrc/mm_latent.hip).
+
+    In fit the same span is vv_mm_latent_train_fwd and vv_mm_latent_train_bwd around the decoder's step on the HIP trainer."""
+
+    def __init__(self, nolbo_structure, backbone_style=None, encoder_backbone=None, learning_rate=1e-4):
+        self._prior_class_str = nolbo_structure['prior_class']
+        self._prior_inst_str = nolbo_structure['prior_inst']
+        self._debug = None         # set to a dict to capture the latent stage's inputs and gradients of the next fit (tests)
+        nolboSingleObject_VAE.__init__(self, nolbo_structure, backbone_style=backbone_style, encoder_backbone=encoder_backbone,
+                                       dropout=False, learning_rate=learning_rate)
+
+    @property
+    def _latent_dim(self):
+        """The decoder's input: the concatenated latent (what getSampledShape and its kin sample)."""
+        return self._enc_backbone_str['z_category_dim'] + self._enc_backbone_str['z_inst_dim']
+
+    def _buildModel(self):
+        nolboSingleObject_VAE._buildModel(self)
+        # ==============set prior network (nolbo.py:85-87)
+        self._priornet_class = priornet.priornet(structure=self._prior_class_str, device=self._device)
+        self._priornet_inst = priornet.priornet(structure=self._prior_inst_str, device=self._device)
+
+    def _latent_torch(self, e, pri, eps, eps_p, noise, cat_oh):
+        """fit's latent algebra (nolbo.py:101-140, function.py:40-98) as torch autograd code: what vv_mm_latent_train_fwd / _bwd compute,
+        kept as the comparison leg (latent='torch').  -> z_in [B, Lc+Li], kl [B], reg [B]."""
+        Lc, Li = self._enc_backbone_str['z_category_dim'], self._enc_backbone_str['z_inst_dim']
+        mean_cp, lv_cp, mean_ip, lv_ip = pri
+        mean = torch.cat([e[:, :Lc], e[:, 2 * Lc:2 * Lc + Li]], dim=1)
+        lv = torch.clamp(torch.cat([e[:, Lc:2 * Lc], e[:, 2 * Lc + Li:]], dim=1), -10.0, 10.0)
+        mean_p, lv_p = torch.cat([mean_cp, mean_ip], dim=1), torch.cat([lv_cp, lv_ip], dim=1)
+        z = mean + torch.sqrt(torch.exp(lv)) * eps                                    # function.py:35-38
+        z_prior = mean_p + torch.sqrt(torch.exp(lv_p)) * eps_p
+        z_in = z if noise is None else torch.where(noise == 0, z, z_prior)            # :122-123
+        kl = (0.5 * (lv_p - lv) + (torch.exp(lv) + (mean - mean_p) ** 2) / (2.0 * torch.exp(lv_p)) - 0.5).sum(-1)
+
+        def reg(m, l, dist, cls=None):
+            d = (torch.abs(m[:, None, :] - m[None, :, :]) / torch.exp(0.5 * l)[:, None, :]).sum(-1) - dist
+            v = torch.where(d > 0, torch.zeros_like(d), d * d)
+            if cls is not None:                                                       # only pairs of one class count
+                v = v * (torch.abs(cls[:, None, :] - cls[None, :, :]).sum(-1) <= 0).to(v.dtype)
+            return v.sum(-1)
+
+        return z_in, kl, reg(mean_cp, lv_cp, 3.0 * Lc) + reg(mean_ip, lv_ip, 3.0 * Li, cat_oh)
+
+    def fit(self, inputs, *, latent='hip', _rand=None):
+        """nolbo.py:90-159: (input_images, output_images, category_list, inst_list) -> (loss_kl, loss_shape, loss_reg, pr, rc);
+        total = mean KL(q || priors) + shape + mean reg + the l2 terms of all five sub-models.  The head output and the two prior
+        networks run in torch; between them and the decoder step (voxvae.train.Trainer.step_decoder) the latent stage is ONE
+        vv_mm_latent_train_fwd and, with the decoder's d shape / d z_in, ONE vv_mm_latent_train_bwd; its gradients continue through
+        the 2D encoder and the prior networks by torch autograd; Adam on all of them.  latent='torch' runs the same algebra as an
+        autograd closure.  `_rand` (tests) = dict(eps, eps_prior [B, Lc+Li], mix (bool), noise [B, Lc+Li])."""
+        from voxvae import train as _T
+        if latent not in ('hip', 'torch'):
+            raise ValueError("latent must be 'hip' or 'torch', got %r" % (latent,))
+        input_images, output_images, category_list, inst_list = inputs
+        Lc, Li = self._enc_backbone_str['z_category_dim'], self._enc_backbone_str['z_inst_dim']
+        y, cat_oh, inst_oh = self._dev(output_images), self._dev(category_list).contiguous(), self._dev(inst_list).contiguous()
+        if getattr(self, '_trainer_mm', None) is None:
+            self._trainer_mm = _T.Trainer(None, self._dec_eng, variational=False, learning_rate=self._learning_rate)
+            mods = [m for m in (self._encoder_backbone, self._encoder_head, self._priornet_class, self._priornet_inst)
+                    if isinstance(m, torch.nn.Module)]
+            self._opt_mm = torch.optim.Adam([p for m in mods for p in m.parameters()], lr=self._learning_rate, eps=1e-7)   # Keras epsilon
+        self._opt_mm.zero_grad(set_to_none=True)
+        pri = self._priornet_class(cat_oh, training=True) + self._priornet_inst(torch.cat([cat_oh, inst_oh], dim=-1), training=True)   # :95-97
+        enc_out = self._encoder_2d(input_images, training=True)                      # :100
+        if not (torch.is_tensor(enc_out) and enc_out.requires_grad):                  # a 2D encoder without parameters, or head outputs
+            enc_out = self._dev(enc_out)
+        B, C = enc_out.shape[0], cat_oh.shape[1]
+        if enc_out.dim() != 2 or enc_out.shape[1] != 2 * Lc + 2 * Li:
+            raise ValueError('the encoder must emit [B, %d] (mean_c | logVar_c | mean_i | logVar_i), got %s' % (2 * Lc + 2 * Li, tuple(enc_out.shape)))
+        r = _rand or {}
+        eps, eps_p = self._draw_eps(B, r.get('eps')).contiguous(), self._draw_eps(B, r.get('eps_prior')).contiguous()
+        mix = bool(r['mix']) if 'mix' in r else not (np.random.rand() > 0.5)          # :119: z itself with probability 1/2
+        noise = None
+        if mix:                                                                       # :122, the same RNG call
+            noise = self._dev(r['noise'] if 'noise' in r else
+                              np.random.choice(a=[False, True], size=(B, Lc + Li), p=[0.5, 0.5]).astype('float32')).contiguous()
+        l2 = [l for m in (self._encoder_head, self._encoder_backbone, self._priornet_class, self._priornet_inst) if hasattr(m, 'losses')
+              for l in m.losses]                                                      # :142-144; the decoder's: step_decoder(l2=)
+        l2 = [torch.stack(l2).sum()] if l2 else []
+        e = enc_out.detach().float().contiguous()
+        if latent == 'torch':
+            e.requires_grad_(True)
+            with torch.enable_grad():
+                z_in, kl, reg = self._latent_torch(e, pri, eps, eps_p, noise, cat_oh)
+                extra = kl.mean() + reg.mean()
+            for t in pri:
+                if self._debug is not None and t.requires_grad:
+                    t.retain_grad()
+            _, m, dz = self._trainer_mm.step_decoder(z_in.detach().contiguous(), y, l2=ae3D.L2_REG)
+            torch.autograd.backward([z_in, extra] + l2, [dz, torch.ones_like(extra)] + [torch.ones_like(t) for t in l2])
+            d_e, d_pri = e.grad, [t.grad if self._debug is not None and t.requires_grad else None for t in pri]
+            if enc_out.requires_grad:
+                enc_out.backward(d_e)
+        else:
+            p = [t.detach().float().contiguous() for t in pri]
+            new = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=self._device)
+            z_in, kl, reg = new(B, Lc + Li), new(B), new(B)
+            z_act = new(B, Lc + Li, dt=torch.bfloat16) if self._act_dt != _L.VV_F32 else None
+            common = (_L.ptr(e), _L.ptr(eps), _L.ptr(p[0]), _L.ptr(p[1]), _L.ptr(p[2]), _L.ptr(p[3]), _L.ptr(eps_p), _L.ptr(noise), _L.ptr(cat_oh))
+            _L.call('vv_mm_latent_train_fwd', *common, _L.ptr(z_in), _L.ptr(z_act), self._act_dt, _L.ptr(kl), _L.ptr(reg), B, Lc, Li, C, _st())
+            _, m, dz = self._trainer_mm.step_decoder(z_in, y, z_act=z_act, l2=ae3D.L2_REG)
+            d_e = new(B, 2 * Lc + 2 * Li)
+            d_pri = [new(*t.shape) if t.requires_grad else None for t in pri]         # a constant log-variance has no gradient
+            _L.call('vv_mm_latent_train_bwd', *common, _L.ptr(dz.contiguous()), 1.0 / B, _L.ptr(d_e), *[_L.ptr(g) for g in d_pri],
+                    B, Lc, Li, C, _st())
+            heads = [(t, g) for t, g in zip(pri, d_pri) if g is not None] + ([(enc_out, d_e)] if enc_out.requires_grad else [])
+            torch.autograd.backward([t for t, _ in heads] + l2, [g for _, g in heads] + [torch.ones_like(t) for t in l2])
+        self._opt_mm.step()
+        if self._debug is not None:
+            self._debug.update({'enc_out': e.detach(), 'pri': [t.detach() for t in pri], 'z_in': z_in.detach(), 'dz_in': dz, 'd_enc_out': d_e,
+                                'd_pri': d_pri})
+        return DeviceArray(kl.detach().mean()), DeviceArray(m[0]), DeviceArray(reg.detach().mean()), DeviceArray(m[1]), DeviceArray(m[2])
+
+    def _prior_means(self, category_list, category_indices, inst_indices, training):
+        """prior_cat [C, Lc] and the instance prior's means of each sample [B, I, Li] (nolbo.py:166-181)."""
+        cat_l = np.asarray(np.array(category_list), dtype=np.float32)
+        inst_ind = np.asarray(inst_indices, dtype=np.float32)
+        B, I = cat_l.shape[0], inst_ind.shape[0]
+        inst_in = np.concatenate([np.repeat(cat_l, I, axis=0), np.tile(inst_ind, (B, 1))], axis=-1)
+        prior_cat, _ = self._priornet_class(np.asarray(category_indices, dtype=np.float32), training=training)
+        prior_inst, _ = self._priornet_inst(inst_in, training=training)
+        return prior_cat.detach().float().contiguous(), prior_inst.detach().float().reshape(B, I, -1).contiguous()
+
+    def getEval(self, inputs, category_indices=np.identity(12), inst_indices=np.identity(10), training=False, missing_prob=0.0, *,
+                _eps=None, _mask=None, _eps2=None):
+        """reference nolbo.py:161-259 -> (pred, loss_shape, pr, rc, acc_cat, acc_inst) at missing_prob == 0, else these and
+        (pred_corrected, loss_shape_corrected, pr_corrected, rc_corrected, acc_cat_corrected).  `_eps` [B, Lc+Li] (the category
+        draw, then the instance draw), `_mask` [B, Lc] and `_eps2` [B, Lc] inject the draws."""
+        input_images, output_images, category_list, inst_list = inputs
+        Lc, Li = self._enc_backbone_str['z_category_dim'], self._enc_backbone_str['z_inst_dim']
+        prior_cat, prior_inst = self._prior_means(category_list, category_indices, inst_indices, training)
+        enc_out = self._enc_out(input_images, training=training)
+        B, C, I = enc_out.shape[0], prior_cat.shape[0], prior_inst.shape[1]
+        if enc_out.dim() != 2 or enc_out.shape[1] != 2 * Lc + 2 * Li:
+            raise ValueError('the encoder must emit [B, %d] (mean_c | logVar_c | mean_i | logVar_i), got %s' % (2 * Lc + 2 * Li, tuple(enc_out.shape)))
+        y, cat_oh, inst_oh = self._dev(output_images), self._dev(category_list).contiguous(), self._dev(inst_list).contiguous()
+        eps = self._draw_eps(B, _eps).contiguous()
+        mask = eps2 = None
+        if missing_prob > 0:
+            if _mask is None:                                                          # :202-203, the same RNG call
+                _mask = np.reshape(np.random.choice(2, B * Lc, p=[missing_prob, 1. - missing_prob]), [B, Lc]).astype('float32')
+            mask = self._dev(_mask).contiguous()
+            eps2 = (torch.randn(B, Lc, dtype=torch.float32, device=self._device) if _eps2 is None else self._dev(_eps2)).contiguous()
+        act_dt = _L.VV_F32 if training else self._act_dt                               # training: float32 to the decoder entry (_eval_hooks)
+        new = lambda dt=torch.float32: torch.empty(B, Lc + Li, dtype=dt, device=self._device)
+        z, zc = new(), (new() if mask is not None else None)
+        twin = act_dt != _L.VV_F32
+        z_act, zc_act = (new(torch.bfloat16) if twin else None), (new(torch.bfloat16) if twin and mask is not None else None)
+        idx = torch.empty(B, 4, dtype=torch.int32, device=self._device)
+        acc = torch.empty(3, dtype=torch.float32, device=self._device)
+        _L.call('vv_mm_latent_eval', _L.ptr(enc_out), _L.ptr(eps), _L.ptr(mask), _L.ptr(eps2), _L.ptr(prior_cat), _L.ptr(prior_inst),
+                _L.ptr(cat_oh), _L.ptr(inst_oh), _L.ptr(z), _L.ptr(zc), _L.ptr(z_act), _L.ptr(zc_act), act_dt, _L.ptr(idx), _L.ptr(acc),
+                B, Lc, Li, C, I, _st())
+        decode = self._eval_hooks(training)[1]
+        pred, _, m = decode(z_act if twin else z, y, None)                             # :229-235
+        self._z, self._nearest = DeviceArray(z), DeviceArray(idx)
+        res = self._scored(pred, m) + (DeviceArray(acc[0]), DeviceArray(acc[1]))
+        if missing_prob == 0.0:
+            return res
+        pred_c, _, mc = decode(zc_act if twin else zc, y, None)                        # :252-258
+        self._z_corrected = DeviceArray(zc)
+        return res + self._scored(pred_c, mc) + (DeviceArray(acc[2]),)
+
+    def savePriorCategory(self, save_path):
+        self._priornet_class.save_weights(os.path.join(save_path, self._prior_class_str['name']))
+
+    def savePriorInst(self, save_path):
+        self._priornet_inst.save_weights(os.path.join(save_path, self._prior_inst_str['name']))
+
+    def saveModel(self, save_path):
+        self.saveEncoder(save_path)
+        self.saveDecoder(save_path)
+        self.savePriorCategory(save_path)
+        self.savePriorInst(save_path)
+
+    def loadPriorCategory(self, load_path, file_name=None):
+        self._priornet_class.load_weights(os.path.join(load_path, self._prior_class_str['name'] if file_name is None else file_name))
+
+    def loadPriorInst(self, load_path, file_name=None):
+        self._priornet_inst.load_weights(os.path.join(load_path, self._prior_inst_str['name'] if file_name is None else file_name))
+
+    def loadModel(self, load_path):
+        self.loadEncoder(load_path)
+        self.loadDecoder(load_path)
+        self.loadPriorCategory(load_path)
+        self.loadPriorInst(load_path)
+
+
+class nolboSingleObject_AE(nolboSingleObject_VAE):
+    """The reference's image -> 3D autoencoder, nolbo.py:541-748 (the AE baseline of test_pascal_3D.py): nolboSingleObject_VAE without
+    the sampling -- the head output [B, z_dim] IS the latent.  getEval (the 10-tuple, :632-698) and getLatent are _ModelnetBase's
+    non-variational forms; fit (:580-610) trains the 2D encoder by torch autograd and the decoder through the HIP trainer's
+    decoder-only step; save / load are nolboSingleObject_VAE's."""
+    _variational = False
+
+    def _latent_training_mode(self, x, eps=None):
+        with torch.no_grad():
+            z = self._enc_out(x, training=True)
+        return z, z, None, None
+
+    def fit(self, inputs, *, _dropout=None):
+        """nolbo.py:580-610: (input_images, output_images) -> (loss_shape, pr, rc); total = shape + the l2 terms of head, backbone
+        and decoder.  dropout=True: inverted dropout on z at a rate ~ U[0,1) per step (:586-588); `_dropout` = (rate, keep [B, L])
+        injects it."""
+        from voxvae import train as _T
+        input_images, output_images = inputs
+        y = self._dev(output_images)
+        if self._trainer2d is None:
+            self._trainer2d = _T.Trainer(None, self._dec_eng, variational=False, learning_rate=self._learning_rate)
+            mods = [m for m in (self._encoder_backbone, self._encoder_head) if isinstance(m, torch.nn.Module)]
+            params = [p for m in mods for p in m.parameters()]
+            self._opt2d = torch.optim.Adam(params, lr=self._learning_rate, eps=1e-7) if params else None   # Keras epsilon
+        z = self._encoder_2d(input_images, training=True)
+        if not (torch.is_tensor(z) and z.requires_grad):
+            z = self._dev(z)
+        z_in, keep = z.detach().float().contiguous(), None
+        if self._dropout:
+            rate, keep = _dropout if _dropout is not None else (float(np.random.rand()), None)
+            keep = (torch.rand(z_in.shape, device=self._device) >= rate).float() if keep is None else self._dev(keep)
+            keep = keep * (1.0 / (1.0 - rate))
+            z_in = z_in * keep
+        _, m, dz = self._trainer2d.step_decoder(z_in, y, l2=ae3D.L2_REG)               # + decoder.losses, :595-596
+        if self._opt2d is not None and z.requires_grad:
+            self._opt2d.zero_grad(set_to_none=True)
+            reg = [l for mod in (self._encoder_head, self._encoder_backbone) if hasattr(mod, 'losses') for l in mod.losses]
+            reg = [torch.stack(reg).sum()] if reg else []
+            torch.autograd.backward([z] + reg, [dz if keep is None else dz * keep] + [torch.ones_like(t) for t in reg])
+            self._opt2d.step()
+        return DeviceArray(m[0]), DeviceArray(m[1]), DeviceArray(m[2])

@@ -105,6 +105,12 @@ SIGNATURES = {
     'vv_detect_decode': (_i, [_vp] + [_i] * 7 + [_f, _f, _i] + [_vp] * 9 + [_vp]),
     'vv_detect_decode_host': (_i, [_vp] + [_i] * 7 + [_f, _f, _i] + [_vp] * 9),
     'vv_detect_activation_host': (_i, [_vp, _vp, _l, _i]),
+    'vv_mm_latent_eval': (_i, [_vp] * 12 + [_i, _vp, _vp] + [_i] * 5 + [_vp]),
+    'vv_mm_latent_eval_host': (_i, [_vp] * 12 + [_i, _vp, _vp] + [_i] * 5),
+    'vv_mm_latent_train_fwd': (_i, [_vp] * 11 + [_i, _vp, _vp] + [_i] * 4 + [_vp]),
+    'vv_mm_latent_train_fwd_host': (_i, [_vp] * 11 + [_i, _vp, _vp] + [_i] * 4),
+    'vv_mm_latent_train_bwd': (_i, [_vp] * 10 + [_f] + [_vp] * 5 + [_i] * 4 + [_vp]),
+    'vv_mm_latent_train_bwd_host': (_i, [_vp] * 10 + [_f] + [_vp] * 5 + [_i] * 4),
     'vv_conv2d_packed_bytes': (_sz, [_i, _i, _i, _i]),
     'vv_pack_conv2d': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'vv_conv2d_supported': (_i, [_i] * 5),

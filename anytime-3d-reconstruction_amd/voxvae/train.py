@@ -497,13 +497,36 @@ class Trainer:
         inv_gb = 1.0 / float(B * self.world)
         kl, stats, metrics, de = self._latent_decoder(enc_out, y, eps, drop_mask, drop_scale, B, inv_gb)
         self.overlap = overlap
-        if l2 > 0:      # + sum(decoder.losses) in the total loss (nolbo.py:819-823): d/dw of l2 * sum(w^2)
+        self._add_l2(l2)
+        self._apply()
+        return kl, stats, metrics, de
+
+    def _add_l2(self, l2):
+        """+ sum(decoder.losses) in the total loss (nolbo.py:819-823): d/dw of l2 * sum(w^2)."""
+        if l2 > 0:
             self._join_wgrad()
             for name, _ in self.order:
                 if name.endswith('/kernel') or name == 'dec/dense/bias':
                     self._g(name).add_(self._p(name), alpha=2.0 * l2 / self.world)
+
+    def step_decoder(self, z_in, y, z_act=None, l2=0.0):
+        """Decoder-only step on a latent formed by the caller (the multi-modal model and the image -> 3D autoencoder, nolbo.py:90-159,
+        :565-603): z_in float32 [B, L] is the decoder's input, z_act its activation-dtype copy when the caller has one (cast here
+        otherwise).  Trains the decoder and returns (stats, metrics, d shape / d z_in), the gradient scaled by 1 / global batch: the
+        decoder half of step_custom_latent with the l2 handling of step_from_latent."""
+        self._begin(self.dec, step=True)
+        overlap, self.overlap = self.overlap, self.overlap and l2 == 0
+        B = z_in.shape[0]
+        z_act = self._cast(z_in) if z_act is None else z_act
+        fw = self._decoder_forward(z_act, y, B)
+        var, self.var = self.var, False                      # the latent is the caller's: _decoder_backward ends at d z_in
+        try:
+            dz = self._decoder_backward(fw, y, z_in, None, z_in, z_act, None, 1.0, B, 1.0 / float(B * self.world))
+        finally:
+            self.var, self.overlap = var, overlap
+        self._add_l2(l2)
         self._apply()
-        return kl, stats, metrics, de
+        return fw['stats'], fw['metrics'], dz
 
     def step_custom_latent(self, x, y, latent_fn):
         """Full step with the latent algebra supplied by the caller as torch autograd code (the class-conditional prior

@@ -466,6 +466,66 @@ int vv_detect_decode_host(const float *head, int layout, int batch, int grid_row
 int vv_detect_activation_host(const float *x, float *y, long n, int which);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * The latent stage of the multi-modal model nolboSingleObject (src/module/nolbo.py:49-324): everything between the image encoder's head
+ * output and the decoder's input.  enc_out float32 [B, 2 Lc + 2 Li] = [mean_c | logVar_c | mean_i | logVar_i]; every latent-shaped array
+ * is [category (Lc) | instance (Li)], float32.  1 <= Lc, Li <= 64; 1 <= classes, insts <= 256; B >= 1; else VV_ERR_SHAPE.  NULL and shape
+ * checks come before any launch.  Pointers need the alignment of their element type and no more.  The arithmetic is csrc/mm_latent.h:
+ * float32, exp from csrc/detect_decode.h, correctly rounded division and square root, no contraction, every sum in one fixed order, no
+ * atomics -- the same bits on every run, and the *_host entries (the same header in loops on the CPU, host pointers, no stream) agree
+ * with the device entries bit for bit.
+ *
+ * vv_mm_latent_eval  (getEval, nolbo.py:183-252; two launches: a workgroup per sample, then one workgroup for the accuracies)
+ *   eps [B, Lc+Li]      the category draw, then the instance draw (the order of the reference's two `sampling` calls, :196-197)
+ *   mask [B, Lc]        in {0,1}: the np.random.choice draw of :202, or NULL (missing_prob == 0);  eps2 [B, Lc]: the draw of :242,
+ *                       required exactly when mask is given (a mismatch is VV_ERR_NULL)
+ *   prior_cat [C, Lc]   the category prior's means;  prior_inst [B, I, Li]: the instance prior's means of EACH sample (:166-181)
+ *   cat_onehot [B, C], inst_onehot [B, I]
+ *   z [B, Lc+Li]        logVar clipped to [-10, 10]; z = mean + sqrt(exp(logVar)) eps (:185-197); with a mask the category half is
+ *                       z_c mask, and every element of it that compares equal to 0 -- an unmasked +-0 too -- takes the column mean of
+ *                       prior_cat (:204-208).  The instance half is never masked.
+ *   z_corr [B, Lc+Li]   mask given (then required): where(mask == 0, prior_cat[idx 2] + eps2, z_c) | z_i (:239-252)
+ *   z_act, z_corr_act   optional: the same values as act_dtype (VV_F32 / VV_BF16, round to nearest even); any other act_dtype with one of
+ *                       them given is VV_ERR_DTYPE
+ *   idx int32 [B, 4]    first argmin of the squared distance: z_c to prior_cat (:218-219), z_i to prior_inst[b] (:225-226), the masked
+ *                       distance sum_j mask_j (z_c - P)_j^2 (:239-240), z_c_corr to prior_cat (:248-249).  Only distances below +inf
+ *                       compete; a row that has none gets 0.  Without a mask columns 2 and 3 repeat column 0.
+ *   acc float32 [3]     acc_cat, acc_inst, acc_cat_corrected against the first argmax of the one-hots (:219-227, :249-250); without a mask
+ *                       acc[2] = acc[0]. */
+int vv_mm_latent_eval(const float *enc_out, const float *eps, const float *mask, const float *eps2, const float *prior_cat,
+                      const float *prior_inst, const float *cat_onehot, const float *inst_onehot, float *z, float *z_corr, void *z_act,
+                      void *z_corr_act, int act_dtype, int *idx, float *acc, int batch, int lc, int li, int classes, int insts,
+                      void *hip_stream);
+int vv_mm_latent_eval_host(const float *enc_out, const float *eps, const float *mask, const float *eps2, const float *prior_cat,
+                           const float *prior_inst, const float *cat_onehot, const float *inst_onehot, float *z, float *z_corr, void *z_act,
+                           void *z_corr_act, int act_dtype, int *idx, float *acc, int batch, int lc, int li, int classes, int insts);
+/* vv_mm_latent_train_fwd  (fit, nolbo.py:93-140; one launch)
+ *   mean_cp, lv_cp [B, Lc]; mean_ip, lv_ip [B, Li]   the two prior networks' outputs for each sample (:95-97), not clipped
+ *   eps, eps_p [B, Lc+Li]   the posterior's and the prior's draws (:110-115);  noise [B, Lc+Li] in {0,1} or NULL (:119-123)
+ *   z_in = where(noise == 0, z, z_prior); noise NULL: z_in = z.  z_in_act: optional twin as in vv_mm_latent_eval.
+ *   kl [B]  = kl_loss(category) + kl_loss(instance) against the given priors (function.py:84-98)
+ *   reg [B] = regulizer_loss(mean_cp, lv_cp, 3 Lc) + regulizer_loss(mean_ip, lv_ip, 3 Li, class_input = cat_onehot [B, classes])
+ *             (function.py:40-71): the scale is exp(0.5 lv_i) of row i, the hinge keeps d^2 where d <= 0, the instance term counts the
+ *             pairs whose one-hot rows are equal.
+ * vv_mm_latent_train_bwd  (one launch): for total = mean_b kl + mean_b reg + shape, with dz_in [B, Lc+Li] = d shape / d z_in and
+ *   inv_batch = 1 / B, writes d_enc_out [B, 2 Lc + 2 Li] and the gradients of the four prior outputs (each may be NULL: a constant
+ *   log-variance has none).  A log-variance gradient passes the clip where -10 <= raw <= 10 (as vv_reparam_kl_bwd); d|x|/dx at 0 is 0;
+ *   row i receives the (i, j) and the (j, i) pairs, summed over j in ascending order. */
+int vv_mm_latent_train_fwd(const float *enc_out, const float *eps, const float *mean_cp, const float *lv_cp, const float *mean_ip,
+                           const float *lv_ip, const float *eps_p, const float *noise, const float *cat_onehot, float *z_in, void *z_in_act,
+                           int act_dtype, float *kl, float *reg, int batch, int lc, int li, int classes, void *hip_stream);
+int vv_mm_latent_train_fwd_host(const float *enc_out, const float *eps, const float *mean_cp, const float *lv_cp, const float *mean_ip,
+                                const float *lv_ip, const float *eps_p, const float *noise, const float *cat_onehot, float *z_in,
+                                void *z_in_act, int act_dtype, float *kl, float *reg, int batch, int lc, int li, int classes);
+int vv_mm_latent_train_bwd(const float *enc_out, const float *eps, const float *mean_cp, const float *lv_cp, const float *mean_ip,
+                           const float *lv_ip, const float *eps_p, const float *noise, const float *cat_onehot, const float *dz_in,
+                           float inv_batch, float *d_enc_out, float *d_mean_cp, float *d_lv_cp, float *d_mean_ip, float *d_lv_ip, int batch,
+                           int lc, int li, int classes, void *hip_stream);
+int vv_mm_latent_train_bwd_host(const float *enc_out, const float *eps, const float *mean_cp, const float *lv_cp, const float *mean_ip,
+                                const float *lv_ip, const float *eps_p, const float *noise, const float *cat_onehot, const float *dz_in,
+                                float inv_batch, float *d_enc_out, float *d_mean_cp, float *d_lv_cp, float *d_mean_ip, float *d_lv_ip,
+                                int batch, int lc, int li, int classes);
+
+/* ---------------------------------------------------------------------------------------------------------
  * The image encoder: Darknet19 and head2D (src/net_core/darknet.py:83-94 Darknet19Conv, :96-133 the backbone, :135-168 convHead /
  * head2D) as channels-last 2D layers.  Here grids are NOT cubic and NOT powers of two: x [B,R,C,Cin], any batch, rows, cols >= 1.
  *
