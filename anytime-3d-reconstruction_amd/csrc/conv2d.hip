@@ -17,6 +17,10 @@
 //               written by its own predicate (per (row, tap): the address of such a tap is usually a valid one).
 //   small M   : split-K over gridDim.z into float32 slabs [share][M][Cout], summed share 0, 1, 2, ... by conv2d_splitk_epilogue.
 //               No atomics: two runs give the same bits.
+//   stride 2  : Darknet53Conv(strides=2) (darknet.py:11-31), ZeroPadding2D(((1,0),(1,0))) + 'valid' k3 s2: the same kernel with the GEMM
+//               rows on the floor(R/2) x floor(C/2) output grid and taps at (2 ro + tr - 1, 2 co + tc - 1) of the input (STRIDE).
+//   residual  : Darknet53Residual's `inputs + x` (darknet.py:33-38) is the epilogue's last step, y = act(scale acc + shift) + residual in
+//               float32 before the one rounding (RES), in the GEMM kernel's epilogue and in the split-K epilogue alike: no add launch.
 //   cin = 3   : the float32 image, K = 27 of one 32-chunk.  A direct kernel (one thread per output, fmaf in k order) with the image
 //               rounded to the operand type as it is read: 0.15 G MAC of 9 for a 416 x 416 frame.
 #include "common.h"
@@ -66,11 +70,14 @@ __device__ __forceinline__ void c2_mma_chunk(const char *As, const char *Bs, int
 }
 
 // SPLIT: share blockIdx.z of K goes out raw as slabs[share][M][cout]; otherwise the epilogue runs here.
-template <typename T, typename OT, bool SPLIT>
+// STRIDE 2 (vv_conv2d_ex_fwd): the GEMM rows run over the Ro x Co output grid and a row's taps start at input pixel (2 ro, 2 co); R x C
+// stays the INPUT grid, which is what the tap predicate and the tap offset are about.  RES: y = act(...) + residual[m][ch], added in
+// float32 behind the activation (Darknet53Residual, darknet.py:33-38); with SPLIT the add is the split-K epilogue's.
+template <typename T, typename OT, bool SPLIT, int STRIDE = 1, bool RES = false>
 __global__ __launch_bounds__(256) void conv2d_mfma_kernel(const T *__restrict__ x, const T *__restrict__ w, const float *__restrict__ scale,
                                                           const float *__restrict__ shift, OT *__restrict__ y, float *__restrict__ slabs, int M,
                                                           int R, int C, int cin, int cout, int npad, int ksize, int kchunks, int act,
-                                                          float alpha) {
+                                                          float alpha, const T *__restrict__ residual, int Ro, int Co) {
     constexpr int SLOTS = C2T<T>::SLOTS, EPS = C2T<T>::EPS, SHIFT = C2T<T>::SHIFT;
     constexpr int PASSES = SLOTS * C2_BM / 256;                 // 16-byte loads per thread, operand and chunk
     constexpr int TILE_BYTES = C2_BM * SLOTS * 16;
@@ -92,10 +99,17 @@ __global__ __launch_bounds__(256) void conv2d_mfma_kernel(const T *__restrict__ 
         lslot[p] = idx % SLOTS;
         const long m = (long)m0 + lrow[p];
         live[p] = m < M;
-        const C2Row rc = c2_row(live[p] ? m : 0, R, C);
-        pr[p] = rc.r;
-        pc[p] = rc.c;
-        pix[p] = live[p] ? m : 0;
+        if constexpr (STRIDE == 1) {
+            const C2Row rc = c2_row(live[p] ? m : 0, R, C);
+            pr[p] = rc.r;
+            pc[p] = rc.c;
+            pix[p] = live[p] ? m : 0;
+        } else {
+            const C2Row rc = c2_row(live[p] ? m : 0, Ro, Co);
+            pr[p] = rc.r;
+            pc[p] = rc.c;
+            pix[p] = c2_ex_tap_pixel(rc.b, rc.r, rc.c, ksize / 2, ksize / 2, ksize, STRIDE, R, C);      // the centre tap: offset 0
+        }
     }
     uint4 ra[PASSES], rb[PASSES];
     auto fetch = [&](int kc) {
@@ -104,7 +118,10 @@ __global__ __launch_bounds__(256) void conv2d_mfma_kernel(const T *__restrict__ 
 #pragma unroll
         for (int p = 0; p < PASSES; ++p) {
             ra[p] = uint4{0u, 0u, 0u, 0u};
-            if (live[p] && c2_tap_valid(pr[p], pc[p], tr, tc, ksize, R, C))
+            bool in;
+            if constexpr (STRIDE == 1) in = c2_tap_valid(pr[p], pc[p], tr, tc, ksize, R, C);
+            else in = c2_ex_tap_valid(pr[p], pc[p], tr, tc, ksize, STRIDE, R, C);
+            if (live[p] && in)
                 ra[p] = *reinterpret_cast<const uint4 *>(x + ((pix[p] + off) * cin + ci0 + lslot[p] * EPS));
             rb[p] = *reinterpret_cast<const uint4 *>(w + (((long)kc * npad + n0 + lrow[p]) * C2_KC + lslot[p] * EPS));
         }
@@ -146,28 +163,32 @@ __global__ __launch_bounds__(256) void conv2d_mfma_kernel(const T *__restrict__ 
             if (ch >= cout) continue;
             const float v = acc[4 * g + e];
             if (SPLIT) slabs[((long)blockIdx.z * M + m) * cout + ch] = v;
+            else if (RES) vv_store(y, (size_t)(m * cout + ch), c2_bn_act(v, scale, shift, ch, act, alpha) + vv_load_f32(residual, (size_t)(m * cout + ch)));
             else vv_store(y, (size_t)(m * cout + ch), c2_bn_act(v, scale, shift, ch, act, alpha));
         }
     }
 }
 
 // y = act(scale * (slab 0 + slab 1 + ...) + shift): the shares in index order, whatever order they were computed in
-template <typename OT>
+// RT: the residual's type (the operand type of the convolution); RES as in the GEMM kernel
+template <typename OT, typename RT = OT, bool RES = false>
 __global__ __launch_bounds__(256) void conv2d_splitk_epilogue(const float *__restrict__ slabs, const float *__restrict__ scale,
                                                               const float *__restrict__ shift, OT *__restrict__ y, long total, int cout, int splits,
-                                                              int act, float alpha) {
+                                                              int act, float alpha, const RT *__restrict__ residual) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         float v = slabs[i];
         for (int s = 1; s < splits; ++s) v += slabs[(long)s * total + i];
-        vv_store(y, (size_t)i, c2_bn_act(v, scale, shift, (int)(i % cout), act, alpha));
+        v = c2_bn_act(v, scale, shift, (int)(i % cout), act, alpha);
+        if (RES) v += vv_load_f32(residual, (size_t)i);
+        vv_store(y, (size_t)i, v);
     }
 }
 
 // cin = 3: x is the float32 image; T is the operand type the image is rounded to and the packed weights are stored in
-template <typename T, typename OT>
+template <typename T, typename OT, bool RES = false>
 __global__ __launch_bounds__(256) void conv2d_image_kernel(const float *__restrict__ x, const T *__restrict__ w, const float *__restrict__ scale,
                                                            const float *__restrict__ shift, OT *__restrict__ y, long total, int R, int C, int cout,
-                                                           int ksize, int act, float alpha) {
+                                                           int ksize, int act, float alpha, const T *__restrict__ residual) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long m = i / cout;
         const int co = (int)(i - m * cout);
@@ -182,7 +203,9 @@ __global__ __launch_bounds__(256) void conv2d_image_kernel(const float *__restri
 #pragma unroll
                 for (int ci = 0; ci < 3; ++ci) acc = fmaf(static_cast<float>(static_cast<T>(px[ci])), static_cast<float>(wt[ci]), acc);
             }
-        vv_store(y, (size_t)i, c2_bn_act(acc, scale, shift, co, act, alpha));
+        float v = c2_bn_act(acc, scale, shift, co, act, alpha);
+        if (RES) v += vv_load_f32(residual, (size_t)i);
+        vv_store(y, (size_t)i, v);
     }
 }
 
@@ -220,31 +243,84 @@ __global__ __launch_bounds__(256) void maxpool2d_same_kernel(const T *__restrict
     }
 }
 
+// MaxPool2D(2, 1, 'same') (darknet.py:77, Darknet53Tiny's last pool): the input's grid; the window is clipped at the last row / column
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool2d_s1_same_kernel(const T *__restrict__ x, T *__restrict__ y, long total, int R, int C, int ch) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const long m = i / ch;
+        const int c = (int)(i - m * ch);
+        const C2Row rc = c2_row(m, R, C);
+        const int r1 = c2_pool1_last(rc.r, R), c1 = c2_pool1_last(rc.c, C);
+        const T *img = x + (long)rc.b * R * C * ch + c;
+        float v = vv_load_f32(img, ((size_t)rc.r * C + rc.c) * ch);
+        v = fmaxf(v, vv_load_f32(img, ((size_t)rc.r * C + c1) * ch));
+        v = fmaxf(v, vv_load_f32(img, ((size_t)r1 * C + rc.c) * ch));
+        v = fmaxf(v, vv_load_f32(img, ((size_t)r1 * C + c1) * ch));
+        vv_store(y, (size_t)i, v);
+    }
+}
+
 bool c2_dtype_ok(int dt) { return dt == VV_F32 || dt == VV_BF16; }
 long c2_forced_splits() { return vv_hook_int(vv_hook("VV_C2_SPLITS"), 0); }
 
-template <typename T, typename OT>
-int c2_launch(const void *x, const void *w, const float *scale, const float *shift, void *y, int M, int R, int C, int cin, int cout, int ksize,
-              int act, float alpha, int splits, void *ws, hipStream_t st) {
+// M, Ro, Co: the OUTPUT's rows and grid (= the input's at stride 1); R, C the input grid
+template <typename T, typename OT, int STRIDE, bool RES>
+int c2_launch(const void *x, const void *w, const float *scale, const float *shift, const void *residual, void *y, int M, int R, int C, int Ro, int Co,
+              int cin, int cout, int ksize, int act, float alpha, int splits, void *ws, hipStream_t st) {
     const long total = (long)M * cout;
     if (cin == 3) {
-        VV_LAUNCH((conv2d_image_kernel<T, OT>), dim3(vv_grid_1d(total)), dim3(256), 0, st, (const float *)x, (const T *)w, scale, shift, (OT *)y,
-                  total, R, C, cout, ksize, act, alpha);
+        VV_LAUNCH((conv2d_image_kernel<T, OT, RES>), dim3(vv_grid_1d(total)), dim3(256), 0, st, (const float *)x, (const T *)w, scale, shift, (OT *)y,
+                  total, R, C, cout, ksize, act, alpha, (const T *)residual);
         return vv_launch_status();
     }
     const int kchunks = c2_kchunks(ksize, cin), npad = c2_npad(cout);
     const dim3 grid((M + C2_BM - 1) / C2_BM, npad / C2_BN, splits);
     if (splits == 1) {
-        VV_LAUNCH((conv2d_mfma_kernel<T, OT, false>), grid, dim3(256), 0, st, (const T *)x, (const T *)w, scale, shift, (OT *)y, (float *)nullptr, M, R,
-                  C, cin, cout, npad, ksize, kchunks, act, alpha);
+        VV_LAUNCH((conv2d_mfma_kernel<T, OT, false, STRIDE, RES>), grid, dim3(256), 0, st, (const T *)x, (const T *)w, scale, shift, (OT *)y,
+                  (float *)nullptr, M, R, C, cin, cout, npad, ksize, kchunks, act, alpha, (const T *)residual, Ro, Co);
         return vv_launch_status();
     }
-    VV_LAUNCH((conv2d_mfma_kernel<T, OT, true>), grid, dim3(256), 0, st, (const T *)x, (const T *)w, scale, shift, (OT *)nullptr, (float *)ws, M, R, C, cin,
-              cout, npad, ksize, kchunks, act, alpha);
+    VV_LAUNCH((conv2d_mfma_kernel<T, OT, true, STRIDE, false>), grid, dim3(256), 0, st, (const T *)x, (const T *)w, scale, shift, (OT *)nullptr,
+              (float *)ws, M, R, C, cin, cout, npad, ksize, kchunks, act, alpha, (const T *)nullptr, Ro, Co);
     if (const int s = vv_launch_status()) return s;
-    VV_LAUNCH((conv2d_splitk_epilogue<OT>), dim3(vv_grid_1d(total)), dim3(256), 0, st, (const float *)ws, scale, shift, (OT *)y, total, cout, splits, act,
-              alpha);
+    VV_LAUNCH((conv2d_splitk_epilogue<OT, T, RES>), dim3(vv_grid_1d(total)), dim3(256), 0, st, (const float *)ws, scale, shift, (OT *)y, total, cout,
+              splits, act, alpha, (const T *)residual);
     return vv_launch_status();
+}
+
+// the one body of vv_conv2d_fwd (stride 1, no residual) and vv_conv2d_ex_fwd: every refusal is decided here, before any launch
+int c2_forward(const void *x, const void *w_packed, const float *scale, const float *shift, const void *residual, void *y, int batch, int rows,
+               int cols, int cin, int cout, int ksize, int stride, int act, float alpha, int dtype, int out_dtype, void *workspace,
+               size_t workspace_bytes, void *hip_stream) {
+    if (!x || !w_packed || !y) return VV_ERR_NULL;
+    if (!c2_ex_shape_ok(ksize, stride, cin, cout) || !c2_ex_extent_ok(batch, rows, cols, stride, cin, cout)) return VV_ERR_SHAPE;
+    if (!c2_dtype_ok(dtype) || !c2_dtype_ok(out_dtype)) return VV_ERR_DTYPE;
+    if (act < VV_ACT_NONE || act > VV_ACT_LRELU) return VV_ERR_SHAPE;
+    if (!vv_aligned16(x) || !vv_aligned16(w_packed) || !vv_aligned16(y) || !vv_aligned16(residual)) return VV_ERR_ALIGN;
+    const int Ro = c2_out_extent(rows, stride), Co = c2_out_extent(cols, stride), M = batch * Ro * Co;
+    const int splits = c2_splits(M, ksize, cin, cout, c2_forced_splits());
+    const size_t need = splits > 1 ? (size_t)splits * M * cout * sizeof(float) : 0;
+    if (need && (!workspace || workspace_bytes < need)) return VV_ERR_WORKSPACE;
+    if (need && !vv_aligned16(workspace)) return VV_ERR_ALIGN;
+    const hipStream_t st = (hipStream_t)hip_stream;
+#define C2_GO4(T, OT, S, RES) return c2_launch<T, OT, S, RES>(x, w_packed, scale, shift, residual, y, M, rows, cols, Ro, Co, cin, cout, ksize, act, alpha, splits, workspace, st)
+#define C2_GO(T, OT)                          \
+    do {                                      \
+        if (stride == 2) {                    \
+            if (residual) C2_GO4(T, OT, 2, true); \
+            C2_GO4(T, OT, 2, false);          \
+        }                                     \
+        if (residual) C2_GO4(T, OT, 1, true); \
+        C2_GO4(T, OT, 1, false);              \
+    } while (0)
+    if (dtype == VV_BF16) {
+        if (out_dtype == VV_BF16) C2_GO(__bf16, __bf16);
+        C2_GO(__bf16, float);
+    }
+    if (out_dtype == VV_BF16) C2_GO(float, __bf16);
+    C2_GO(float, float);
+#undef C2_GO
+#undef C2_GO4
 }
 
 }  // namespace
@@ -286,25 +362,30 @@ VV_EXPORT int vv_pack_conv2d(const float *w_keras, void *packed, int ksize, int 
 VV_EXPORT int vv_conv2d_fwd(const void *x, const void *w_packed, const float *scale, const float *shift, void *y, int batch, int rows, int cols,
                             int cin, int cout, int ksize, int act, float alpha, int dtype, int out_dtype, void *workspace, size_t workspace_bytes,
                             void *hip_stream) {
-    if (!x || !w_packed || !y) return VV_ERR_NULL;
-    if (!c2_shape_ok(ksize, cin, cout) || !c2_extent_ok(batch, rows, cols, cin, cout)) return VV_ERR_SHAPE;
-    if (!c2_dtype_ok(dtype) || !c2_dtype_ok(out_dtype)) return VV_ERR_DTYPE;
-    if (act < VV_ACT_NONE || act > VV_ACT_LRELU) return VV_ERR_SHAPE;
-    if (!vv_aligned16(x) || !vv_aligned16(w_packed) || !vv_aligned16(y)) return VV_ERR_ALIGN;
-    const int M = batch * rows * cols;
-    const int splits = c2_splits(M, ksize, cin, cout, c2_forced_splits());
-    const size_t need = splits > 1 ? (size_t)splits * M * cout * sizeof(float) : 0;
-    if (need && (!workspace || workspace_bytes < need)) return VV_ERR_WORKSPACE;
-    if (need && !vv_aligned16(workspace)) return VV_ERR_ALIGN;
-    const hipStream_t st = (hipStream_t)hip_stream;
-#define C2_GO(T, OT) return c2_launch<T, OT>(x, w_packed, scale, shift, y, M, rows, cols, cin, cout, ksize, act, alpha, splits, workspace, st)
-    if (dtype == VV_BF16) {
-        if (out_dtype == VV_BF16) C2_GO(__bf16, __bf16);
-        C2_GO(__bf16, float);
-    }
-    if (out_dtype == VV_BF16) C2_GO(float, __bf16);
-    C2_GO(float, float);
-#undef C2_GO
+    return c2_forward(x, w_packed, scale, shift, nullptr, y, batch, rows, cols, cin, cout, ksize, 1, act, alpha, dtype, out_dtype, workspace,
+                      workspace_bytes, hip_stream);
+}
+
+VV_EXPORT int vv_conv2d_ex_supported(int ksize, int stride, int cin, int cout, int dtype, int out_dtype) {
+    return c2_ex_shape_ok(ksize, stride, cin, cout) && c2_dtype_ok(dtype) && c2_dtype_ok(out_dtype) ? 1 : 0;
+}
+
+VV_EXPORT int vv_conv2d_ex_splits(int batch, int rows, int cols, int ksize, int stride, int cin, int cout) {
+    if (!c2_ex_shape_ok(ksize, stride, cin, cout) || !c2_ex_extent_ok(batch, rows, cols, stride, cin, cout)) return 0;
+    return c2_splits((long)batch * c2_out_extent(rows, stride) * c2_out_extent(cols, stride), ksize, cin, cout, c2_forced_splits());
+}
+
+VV_EXPORT size_t vv_conv2d_ex_workspace_bytes(int batch, int rows, int cols, int ksize, int stride, int cin, int cout, int dtype) {
+    const int splits = vv_conv2d_ex_splits(batch, rows, cols, ksize, stride, cin, cout);
+    if (splits <= 1 || !c2_dtype_ok(dtype)) return 0;
+    return (size_t)splits * batch * c2_out_extent(rows, stride) * c2_out_extent(cols, stride) * cout * sizeof(float);
+}
+
+VV_EXPORT int vv_conv2d_ex_fwd(const void *x, const void *w_packed, const float *scale, const float *shift, const void *residual, void *y, int batch,
+                               int rows, int cols, int cin, int cout, int ksize, int stride, int act, float alpha, int dtype, int out_dtype,
+                               void *workspace, size_t workspace_bytes, void *hip_stream) {
+    return c2_forward(x, w_packed, scale, shift, residual, y, batch, rows, cols, cin, cout, ksize, stride, act, alpha, dtype, out_dtype, workspace,
+                      workspace_bytes, hip_stream);
 }
 
 VV_EXPORT int vv_maxpool2d_same_fwd(const void *x, void *y, int batch, int rows, int cols, int channels, int dtype, void *hip_stream) {
@@ -317,5 +398,18 @@ VV_EXPORT int vv_maxpool2d_same_fwd(const void *x, void *y, int batch, int rows,
         VV_LAUNCH(maxpool2d_same_kernel<__bf16>, dim3(vv_grid_1d(total)), dim3(256), 0, st, (const __bf16 *)x, (__bf16 *)y, total, rows, cols, channels);
     else
         VV_LAUNCH(maxpool2d_same_kernel<float>, dim3(vv_grid_1d(total)), dim3(256), 0, st, (const float *)x, (float *)y, total, rows, cols, channels);
+    return vv_launch_status();
+}
+
+VV_EXPORT int vv_maxpool2d_s1_same_fwd(const void *x, void *y, int batch, int rows, int cols, int channels, int dtype, void *hip_stream) {
+    if (!x || !y) return VV_ERR_NULL;
+    if (channels < 1 || !c2_extent_ok(batch, rows, cols, channels, channels)) return VV_ERR_SHAPE;
+    if (!c2_dtype_ok(dtype)) return VV_ERR_DTYPE;
+    const long total = (long)batch * rows * cols * channels;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    if (dtype == VV_BF16)
+        VV_LAUNCH(maxpool2d_s1_same_kernel<__bf16>, dim3(vv_grid_1d(total)), dim3(256), 0, st, (const __bf16 *)x, (__bf16 *)y, total, rows, cols, channels);
+    else
+        VV_LAUNCH(maxpool2d_s1_same_kernel<float>, dim3(vv_grid_1d(total)), dim3(256), 0, st, (const float *)x, (float *)y, total, rows, cols, channels);
     return vv_launch_status();
 }

@@ -43,6 +43,29 @@ C2_HD inline bool c2_tap_valid(int r, int c, int tr, int tc, int ksize, int R, i
 // pixel-index offset of a valid tap relative to its row's own pixel
 C2_HD inline int c2_tap_offset(int tr, int tc, int ksize, int C) { return (tr - ksize / 2) * C + (tc - ksize / 2); }
 
+// The strided form (vv_conv2d_ex_fwd): GEMM rows run over the OUTPUT grid, Ro x Co = c2_out_extent of the input's R x C.  Stride 2 is
+// ZeroPadding2D(((1, 0), (1, 0))) + a 'valid' k3 s2 convolution: output (ro, co) reads input (2 ro + tr - 1, 2 co + tc - 1), so only row
+// and column -1 are padding and, for an odd size, the last input row / column is never read.  Stride 1 is the 'same' form above.
+C2_HD inline int c2_out_extent(int n, int stride) { return stride == 2 ? n / 2 : n; }
+C2_HD inline bool c2_ex_shape_ok(int ksize, int stride, int cin, int cout) {
+    if (!c2_shape_ok(ksize, cin, cout)) return false;
+    return stride == 1 || (stride == 2 && ksize == 3 && cin != 3);
+}
+// Tap (tr, tc) of the output at (ro, co): inside the R x C input or not.  As above the address of an outside tap is usually a valid one
+// (row -1 of image b is the last row of image b - 1), so only this predicate may decide.
+C2_HD inline bool c2_ex_tap_valid(int ro, int co, int tr, int tc, int ksize, int stride, int R, int C) {
+    const int p = ksize / 2, rr = ro * stride + tr - p, cc = co * stride + tc - p;
+    return rr >= 0 && rr < R && cc >= 0 && cc < C;
+}
+// pixel index, in the [B,R,C] input, of a valid tap of output (b, ro, co)
+C2_HD inline long c2_ex_tap_pixel(int b, int ro, int co, int tr, int tc, int ksize, int stride, int R, int C) {
+    return ((long)b * R + ro * stride) * C + co * stride + c2_tap_offset(tr, tc, ksize, C);
+}
+// MaxPool2D(2, 1, 'same') reads (r .. min(r + 1, R - 1), c .. min(c + 1, C - 1)): padding only at the end
+C2_HD inline int c2_pool1_last(int i, int n) { return i + 1 < n ? i + 1 : n - 1; }
+// every tensor of the strided form within 2^31 - 1 elements: the input with cin, the output grid with cout
+C2_HD inline bool c2_ex_extent_ok(long batch, long rows, long cols, int stride, int cin, int cout);
+
 // Split-K: how many shares K is cut into so that a small M still fills 256 CUs.  1 = the direct form (epilogue in the GEMM kernel).
 // `forced` > 0 (test hook) overrides the choice, clamped to what the K extent admits.
 inline int c2_splits(long M, int ksize, int cin, int cout, long forced) {
@@ -77,4 +100,8 @@ C2_HD inline bool c2_extent_ok(long batch, long rows, long cols, int cin, int co
     const long M = batch * rc;
     const long widest = cin > cout ? cin : cout;
     return M <= lim / widest;
+}
+C2_HD inline bool c2_ex_extent_ok(long batch, long rows, long cols, int stride, int cin, int cout) {
+    if (stride != 2) return c2_extent_ok(batch, rows, cols, cin, cout);
+    return rows >= 2 && cols >= 2 && c2_extent_ok(batch, rows, cols, cin, cin) && c2_extent_ok(batch, rows / 2, cols / 2, cout, cout);
 }

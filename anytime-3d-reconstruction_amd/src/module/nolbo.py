@@ -556,6 +556,7 @@ class nolboSingleObject_VAE(_ModelnetBase):
         if self._encoder_backbone is None:
             return x
         f = self._encoder_backbone(x, training=training) if self._encoder_head is not None else self._encoder_backbone(x)
+        f = darknet.last_output(f)                           # Darknet53 / Darknet53Tiny give tuples: the head takes the last map
         return self._encoder_head(f, training=training) if self._encoder_head is not None else f
 
     def _enc_out(self, x, training=False):

@@ -10,7 +10,10 @@ Keras attributes the model classes use: `.output_shape`, `.trainable_variables`,
 
 Keras semantics restated: Conv2D 'same' stride 1 without bias, BatchNormalization(momentum 0.99, epsilon 1e-3),
 ELU / LeakyReLU(0.1) / ReLU, MaxPool2D(2, 2, 'same') (= ceil-mode pooling), Glorot-uniform kernels, and the
-kernel_regularizer l2(0.0005) that only the head's convolutions carry (darknet.py:140-141,160-161).
+kernel_regularizer l2(0.0005) that the head's convolutions (darknet.py:140-141,160-161) and every Darknet53Conv (:20) carry.
+
+`Darknet53(name, activation)` / `Darknet53Tiny(name, activation)` (darknet.py:11-81) return TUPLES of feature maps, (x_36, x_61, x) and
+(x_8, x); `.output_shape` is the last one's, `.output_shapes` lists all, and `last_output` is the rule every caller picks by.
 """
 import numpy as np
 import torch
@@ -31,16 +34,35 @@ def _act(name):
 class _ConvBNAct(nn.Module):
     """Darknet19Conv / convHead (darknet.py:83-94, 137-150): Conv2D(same, no bias) -> BatchNormalization -> activation."""
 
-    def __init__(self, cin, cout, k, activation, l2=0.0):
+    def __init__(self, cin, cout, k, activation, l2=0.0, stride=1):
         super().__init__()
-        self.conv = nn.Conv2d(cin, cout, k, stride=1, padding=k // 2, bias=False)
+        # Darknet53Conv(strides=2) (darknet.py:11-18): ZeroPadding2D(((1, 0), (1, 0))) in forward, then a 'valid' convolution
+        self.stride = stride
+        self.conv = nn.Conv2d(cin, cout, k, stride=stride, padding=k // 2 if stride == 1 else 0, bias=False)
         nn.init.xavier_uniform_(self.conv.weight)
         self.bn = nn.BatchNorm2d(cout, eps=1e-3, momentum=0.01)   # Keras momentum 0.99 = torch momentum 0.01
         self.act = _act(activation)
         self.l2 = l2
 
     def forward(self, x):
+        if self.stride != 1:
+            x = F.pad(x, (1, 0, 1, 0))
         return self.act(self.bn(self.conv(x)))
+
+
+class _Pool1Same(nn.Module):
+    """MaxPool2D(2, 1, 'same') (darknet.py:77): the input's grid, padding only at the end."""
+
+    def forward(self, x):
+        return F.max_pool2d(F.pad(x, (0, 1, 0, 1), value=float('-inf')), 2, 1)
+
+
+def last_output(out):
+    """The feature map a head takes from a backbone's output: the last element of Darknet53's / Darknet53Tiny's tuple (the reference's
+    classifier.py:78-81), the output itself for every other backbone.  Every module here applies it to what it is called on, so
+    `head(backbone(x))` -- the form nolbo_test and the image models use -- works for all three backbones; classifier and the image models
+    also call it themselves where they take the backbone's output."""
+    return out[-1] if isinstance(out, tuple) else out
 
 
 class _Keras2D(nn.Module):
@@ -74,6 +96,7 @@ class _Keras2D(nn.Module):
         return self._chain(x)
 
     def __call__(self, x, training=False):
+        x = last_output(x)                                  # a head called on Darknet53's / Darknet53Tiny's tuple takes the last map
         if not torch.is_tensor(x):
             x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
         x = x.to(self._device, torch.float32)
@@ -159,6 +182,86 @@ class _Head2D(_Keras2D):
         if self.last_pooling == 'average':
             return y.mean(dim=(1, 2))                       # a torch reduction on the float32 head output (include/voxvae.h says so)
         return y
+
+
+class _Darknet53(_Keras2D):
+    """Darknet53 / Darknet53Tiny (darknet.py:11-81) as a flat list of steps: `layers[i]` is a _ConvBNAct or a pool, `_res[i]` the step
+    whose output is added behind step i (Darknet53Residual: inputs + conv3x3(conv1x1(inputs))), `_taps` the steps whose outputs leave
+    the model in front of the last one.  Every kernel carries l2 0.0005 (darknet.py:20)."""
+    L2 = 0.0005
+
+    def __init__(self, name=None, activation='elu', device=None, engine=None, tiny=False):
+        super().__init__(name, device, engine)
+        self.layers, self._res, self._taps, self._widths = nn.ModuleList(), {}, [], []
+        self._cin = 3
+        if tiny:
+            self._build_tiny(activation)
+        else:
+            self._build_53(activation)
+        self.output_shapes = [(None, None, None, self._widths[t]) for t in self._taps] + [(None, None, None, self._cin)]
+        self.output_shape = self.output_shapes[-1]       # what head2D(input_shape=backbone.output_shape[1:]) needs: the LAST output's
+        self._finish()
+
+    def _conv(self, cout, k, activation, stride=1, res=None):
+        self.layers.append(_ConvBNAct(self._cin, cout, k, activation, l2=self.L2, stride=stride))
+        self._cin = cout
+        self._widths.append(cout)
+        if res is not None:
+            self._res[len(self.layers) - 1] = res
+
+    def _pool(self, stride):
+        self.layers.append(nn.MaxPool2d(2, 2, ceil_mode=True) if stride == 2 else _Pool1Same())
+        self._widths.append(self._cin)
+
+    def _build_53(self, activation):
+        self._conv(32, 3, activation)
+        for filters, blocks, tap in ((64, 1, False), (128, 2, False), (256, 8, True), (512, 8, True), (1024, 4, False)):
+            self._conv(filters, 3, activation, stride=2)
+            for _ in range(blocks):
+                src = len(self.layers) - 1
+                self._conv(filters // 2, 1, activation)
+                self._conv(filters, 3, 'elu', res=src)   # darknet.py:35 passes no activation: always ELU, whatever the backbone's is
+            if tap:
+                self._taps.append(len(self.layers) - 1)  # x_36, x_61
+
+    def _build_tiny(self, activation):
+        for filters in (16, 32, 64, 128):
+            self._conv(filters, 3, activation)
+            self._pool(2)
+        self._conv(256, 3, activation)
+        self._taps.append(len(self.layers) - 1)          # x_8
+        self._pool(2)
+        self._conv(512, 3, activation)
+        self._pool(1)
+        self._conv(1024, 3, activation)
+
+    def body(self, x):
+        keep, held = set(self._res.values()) | set(self._taps), {}
+        for i, m in enumerate(self.layers):
+            x = m(x)
+            if i in self._res:
+                src = self._res[i]
+                x = (held[src] if src in self._taps else held.pop(src)) + x      # a block's input is added once: let it go
+            if i in keep:
+                held[i] = x
+        outs = [held[t] for t in self._taps] + [x]
+        return tuple(o.permute(0, 2, 3, 1) for o in outs)
+
+
+def Darknet53(name=None, activation='elu', device=None, engine=None):
+    """-> model(x) = (x_36, x_61, x): strides 8, 16 and 32 (darknet.py:46-56).  engine as for Darknet19."""
+    print('Darknet53', name)
+    m = _Darknet53(name=name, activation=activation, device=device, engine=engine)
+    print('end Darknet53')
+    return m
+
+
+def Darknet53Tiny(name=None, activation='elu', device=None, engine=None):
+    """-> model(x) = (x_8, x): strides 16 and 32 (darknet.py:58-81)."""
+    print('Darknet53Tiny', name)
+    m = _Darknet53(name=name, activation=activation, device=device, engine=engine, tiny=True)
+    print('end Darknet53Tiny')
+    return m
 
 
 def Darknet19(name=None, activation='elu', device=None, engine=None):

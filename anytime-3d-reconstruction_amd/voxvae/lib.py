@@ -118,6 +118,11 @@ SIGNATURES = {
     'vv_conv2d_workspace_bytes': (_sz, [_i] * 7),
     'vv_conv2d_fwd': (_i, [_vp] * 5 + [_i] * 7 + [_f, _i, _i, _vp, _sz, _vp]),
     'vv_maxpool2d_same_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'vv_conv2d_ex_supported': (_i, [_i] * 6),
+    'vv_conv2d_ex_splits': (_i, [_i] * 7),
+    'vv_conv2d_ex_workspace_bytes': (_sz, [_i] * 8),
+    'vv_conv2d_ex_fwd': (_i, [_vp] * 6 + [_i] * 8 + [_f, _i, _i, _vp, _sz, _vp]),
+    'vv_maxpool2d_s1_same_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'vv_latent_mask_fill':(_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     'vv_nearest_category': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     'vv_latent_correct': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -563,6 +563,30 @@ int vv_conv2d_fwd(const void *x, const void *w_packed, const float *scale, const
                   void *hip_stream);
 int vv_maxpool2d_same_fwd(const void *x, void *y, int batch, int rows, int cols, int channels, int dtype, void *hip_stream);
 
+/* The layers Darknet53 / Darknet53Tiny add to that (darknet.py:11-81): a stride-2 convolution, a residual add in the epilogue and the
+ * stride-1 pool.  The same kernels, weights packed by vv_pack_conv2d as for any k3 layer; statuses, limits and alignment as above.
+ *
+ *   stride   1: the 'same' convolution of vv_conv2d_fwd (ksize 1 or 3).  2: ZeroPadding2D(((1,0),(1,0))) + 'valid' k3 s2
+ *            (Darknet53Conv, darknet.py:11-31); ksize == 3, rows, cols >= 2, cin a multiple of 32, else VV_ERR_SHAPE:
+ *              y[b,ro,co,n] = act(scale[n] * sum_{tr,tc,ci} x[b, 2ro+tr-1, 2co+tc-1, ci] * w[tr,tc,ci,n] + shift[n]) (+ residual)
+ *            on the output grid floor(rows/2) x floor(cols/2); a tap with index -1 is zero, and for an odd size the last input row /
+ *            column is never read.  rows, cols are always the INPUT grid.
+ *   residual NULL, or a tensor of y's shape in the operand type `dtype`, 16-byte aligned, not overlapping y:
+ *              y = round_once(act(scale * acc + shift) + residual)
+ *            added in float32 behind the activation (darknet.py:33-38), in the one-launch form and in the split-K epilogue alike (the
+ *            shares still summed 0, 1, 2, ...).  Either stride.
+ *   small M  vv_conv2d_ex_splits / _workspace_bytes decide on the OUTPUT's rows; at stride 1 they equal the queries above.
+ * vv_conv2d_ex_fwd(stride 1, residual NULL) runs the very kernel of vv_conv2d_fwd: the same bits.
+ * vv_maxpool2d_s1_same_fwd: MaxPool2D(2, 1, 'same') (darknet.py:77): y has x's grid, y[r,c] = max x[r..min(r+1,R-1), c..min(c+1,C-1)]
+ *            (padding only at the end).  Exact in either dtype. */
+int vv_conv2d_ex_supported(int ksize, int stride, int cin, int cout, int dtype, int out_dtype);
+int vv_conv2d_ex_splits(int batch, int rows, int cols, int ksize, int stride, int cin, int cout);
+size_t vv_conv2d_ex_workspace_bytes(int batch, int rows, int cols, int ksize, int stride, int cin, int cout, int dtype);
+int vv_conv2d_ex_fwd(const void *x, const void *w_packed, const float *scale, const float *shift, const void *residual, void *y, int batch,
+                     int rows, int cols, int cin, int cout, int ksize, int stride, int act, float alpha, int dtype, int out_dtype,
+                     void *workspace, size_t workspace_bytes, void *hip_stream);
+int vv_maxpool2d_s1_same_fwd(const void *x, void *y, int batch, int rows, int cols, int channels, int dtype, void *hip_stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Training path (nolboSingleObject_modelnet_category_{VAE,AE}.fit, nolbo.py:1411-1447 / 1230-1258).  float32.
  * Data gradients reuse the forward kernels: d(Conv3D k4 s2)/d(input) = vv_convT3d_k4s2_fwd with the SAME Keras
