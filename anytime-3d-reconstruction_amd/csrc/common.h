@@ -134,6 +134,25 @@ static inline void vv_with_act(int act, Fn &&fn) {
     VV_WITH_ACT(act, fn);
 }
 
+// The run-time element-type code as a compile-time type, for the host launchers: vv_with_dtype<float, __bf16>(dtype, fn) calls
+// fn(vv_type<T>{}) for the listed type whose code `dtype` is and returns true; any other code calls nothing and returns false.  fn is
+// instantiated for the listed types only.  vv_dtype_in<Ts...>(dtype) is that answer alone: an entry's validity test and its dispatch
+// name the same list.  vv_dtype_of is where a type gets its code (no other type has one).
+struct vv_fp8;
+template <typename T> struct vv_type { using type = T; };
+template <typename T> struct vv_dtype_of;
+template <> struct vv_dtype_of<float> { static constexpr int code = VV_F32; };
+template <> struct vv_dtype_of<__bf16> { static constexpr int code = VV_BF16; };
+template <> struct vv_dtype_of<vv_fp8> { static constexpr int code = VV_FP8; };
+template <typename... Ts, typename Fn>
+static inline bool vv_with_dtype(int dtype, Fn &&fn) {
+    return ((dtype == vv_dtype_of<Ts>::code ? (fn(vv_type<Ts>{}), true) : false) || ...);
+}
+template <typename... Ts>
+static inline bool vv_dtype_in(int dtype) {
+    return vv_with_dtype<Ts...>(dtype, [](auto) {});
+}
+
 // autoencoder3D.py:33-38: ELU(alpha 1) / ReLU / LeakyReLU(alpha 0.3, the Keras default)
 __device__ __forceinline__ float vv_apply_act(float v, int act) {
     switch (act) {

@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void maxpool2d_s1_same_kernel(const T *__restr
     }
 }
 
-bool c2_dtype_ok(int dt) { return dt == VV_F32 || dt == VV_BF16; }
+bool c2_dtype_ok(int dt) { return vv_dtype_in<float, __bf16>(dt); }
 long c2_forced_splits() { return vv_hook_int(vv_hook("VV_C2_SPLITS"), 0); }
 
 // M, Ro, Co: the OUTPUT's rows and grid (= the input's at stride 1); R, C the input grid
@@ -303,24 +303,22 @@ int c2_forward(const void *x, const void *w_packed, const float *scale, const fl
     if (need && (!workspace || workspace_bytes < need)) return VV_ERR_WORKSPACE;
     if (need && !vv_aligned16(workspace)) return VV_ERR_ALIGN;
     const hipStream_t st = (hipStream_t)hip_stream;
-#define C2_GO4(T, OT, S, RES) return c2_launch<T, OT, S, RES>(x, w_packed, scale, shift, residual, y, M, rows, cols, Ro, Co, cin, cout, ksize, act, alpha, splits, workspace, st)
-#define C2_GO(T, OT)                          \
-    do {                                      \
-        if (stride == 2) {                    \
-            if (residual) C2_GO4(T, OT, 2, true); \
-            C2_GO4(T, OT, 2, false);          \
-        }                                     \
-        if (residual) C2_GO4(T, OT, 1, true); \
-        C2_GO4(T, OT, 1, false);              \
-    } while (0)
-    if (dtype == VV_BF16) {
-        if (out_dtype == VV_BF16) C2_GO(__bf16, __bf16);
-        C2_GO(__bf16, float);
-    }
-    if (out_dtype == VV_BF16) C2_GO(float, __bf16);
-    C2_GO(float, float);
-#undef C2_GO
-#undef C2_GO4
+    int status = VV_ERR_DTYPE;
+    vv_with_dtype<float, __bf16>(dtype, [&](auto t) {
+        vv_with_dtype<float, __bf16>(out_dtype, [&](auto ot) {
+            const auto go = [&](auto stride_c, auto res_c) {
+                status = c2_launch<typename decltype(t)::type, typename decltype(ot)::type, decltype(stride_c)::value, decltype(res_c)::value>(
+                    x, w_packed, scale, shift, residual, y, M, rows, cols, Ro, Co, cin, cout, ksize, act, alpha, splits, workspace, st);
+            };
+            using S1 = std::integral_constant<int, 1>;
+            using S2 = std::integral_constant<int, 2>;
+            if (stride == 2 && residual) go(S2{}, std::true_type{});
+            else if (stride == 2) go(S2{}, std::false_type{});
+            else if (residual) go(S1{}, std::true_type{});
+            else go(S1{}, std::false_type{});
+        });
+    });
+    return status;
 }
 
 }  // namespace
@@ -352,10 +350,10 @@ VV_EXPORT int vv_pack_conv2d(const float *w_keras, void *packed, int ksize, int 
     if (!vv_aligned16(packed)) return VV_ERR_ALIGN;
     const long total = (long)c2_packed_elems(ksize, cin, cout);
     const hipStream_t st = (hipStream_t)hip_stream;
-    if (dtype == VV_BF16)
-        VV_LAUNCH(conv2d_pack_kernel<__bf16>, dim3(vv_grid_1d(total)), dim3(256), 0, st, w_keras, (__bf16 *)packed, total, ksize * ksize * cin, cout, c2_npad(cout));
-    else
-        VV_LAUNCH(conv2d_pack_kernel<float>, dim3(vv_grid_1d(total)), dim3(256), 0, st, w_keras, (float *)packed, total, ksize * ksize * cin, cout, c2_npad(cout));
+    vv_with_dtype<float, __bf16>(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        VV_LAUNCH(conv2d_pack_kernel<T>, dim3(vv_grid_1d(total)), dim3(256), 0, st, w_keras, (T *)packed, total, ksize * ksize * cin, cout, c2_npad(cout));
+    });
     return vv_launch_status();
 }
 
@@ -391,25 +389,23 @@ VV_EXPORT int vv_conv2d_ex_fwd(const void *x, const void *w_packed, const float 
 VV_EXPORT int vv_maxpool2d_same_fwd(const void *x, void *y, int batch, int rows, int cols, int channels, int dtype, void *hip_stream) {
     if (!x || !y) return VV_ERR_NULL;
     if (channels < 1 || !c2_extent_ok(batch, rows, cols, channels, channels)) return VV_ERR_SHAPE;
-    if (!c2_dtype_ok(dtype)) return VV_ERR_DTYPE;
     const long total = (long)batch * ((rows + 1) / 2) * ((cols + 1) / 2) * channels;
     const hipStream_t st = (hipStream_t)hip_stream;
-    if (dtype == VV_BF16)
-        VV_LAUNCH(maxpool2d_same_kernel<__bf16>, dim3(vv_grid_1d(total)), dim3(256), 0, st, (const __bf16 *)x, (__bf16 *)y, total, rows, cols, channels);
-    else
-        VV_LAUNCH(maxpool2d_same_kernel<float>, dim3(vv_grid_1d(total)), dim3(256), 0, st, (const float *)x, (float *)y, total, rows, cols, channels);
-    return vv_launch_status();
+    const bool ok = vv_with_dtype<float, __bf16>(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        VV_LAUNCH(maxpool2d_same_kernel<T>, dim3(vv_grid_1d(total)), dim3(256), 0, st, (const T *)x, (T *)y, total, rows, cols, channels);
+    });
+    return ok ? vv_launch_status() : VV_ERR_DTYPE;
 }
 
 VV_EXPORT int vv_maxpool2d_s1_same_fwd(const void *x, void *y, int batch, int rows, int cols, int channels, int dtype, void *hip_stream) {
     if (!x || !y) return VV_ERR_NULL;
     if (channels < 1 || !c2_extent_ok(batch, rows, cols, channels, channels)) return VV_ERR_SHAPE;
-    if (!c2_dtype_ok(dtype)) return VV_ERR_DTYPE;
     const long total = (long)batch * rows * cols * channels;
     const hipStream_t st = (hipStream_t)hip_stream;
-    if (dtype == VV_BF16)
-        VV_LAUNCH(maxpool2d_s1_same_kernel<__bf16>, dim3(vv_grid_1d(total)), dim3(256), 0, st, (const __bf16 *)x, (__bf16 *)y, total, rows, cols, channels);
-    else
-        VV_LAUNCH(maxpool2d_s1_same_kernel<float>, dim3(vv_grid_1d(total)), dim3(256), 0, st, (const float *)x, (float *)y, total, rows, cols, channels);
-    return vv_launch_status();
+    const bool ok = vv_with_dtype<float, __bf16>(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        VV_LAUNCH(maxpool2d_s1_same_kernel<T>, dim3(vv_grid_1d(total)), dim3(256), 0, st, (const T *)x, (T *)y, total, rows, cols, channels);
+    });
+    return ok ? vv_launch_status() : VV_ERR_DTYPE;
 }

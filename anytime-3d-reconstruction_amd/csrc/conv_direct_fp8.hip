@@ -231,7 +231,7 @@ VV_EXPORT int vv_conv3d_k4s2_direct_fp8_supported(int side, int cin, int cout) {
 VV_EXPORT int vv_conv3d_k4s2_direct_fp8_fwd(const void *x, const void *w_packed, const float *scale, const float *shift, void *y,
                                             int batch, int side, int cin, int cout, int act, int out_dtype, void *stream) {
     if (!x || !w_packed || !y) return VV_ERR_NULL;
-    if (out_dtype != VV_BF16 && out_dtype != VV_FP8) return VV_ERR_DTYPE;
+    if (!vv_dtype_in<__bf16, vv_fp8>(out_dtype)) return VV_ERR_DTYPE;
     if (!vv_conv3d_k4s2_direct_fp8_supported(side, cin, cout) || batch <= 0) return VV_ERR_SHAPE;
     if (!vv_aligned16(x) || !vv_aligned16(w_packed) || !vv_aligned16(y)) return VV_ERR_ALIGN;
     const size_t xb = (size_t)batch * side * side * side * cin;

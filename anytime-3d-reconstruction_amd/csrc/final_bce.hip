@@ -534,7 +534,7 @@ void finish_stats(const float *partials, float *stats, float *metrics4, int nblk
 int final_bce_impl(const void *x, const float *w_keras, const float *target, float *probs, float *logits, float *stats, float *metrics4,
                    int batch, int side, int cin, float gamma, float epsilon, int dtype, void *workspace, size_t workspace_bytes, void *stream) {
     if (!x || !w_keras || !target || !stats) return VV_ERR_NULL;
-    if (dtype != VV_F32 && dtype != VV_BF16 && dtype != VV_FP8) return VV_ERR_DTYPE;
+    if (!vv_dtype_in<float, __bf16, vv_fp8>(dtype)) return VV_ERR_DTYPE;
     if (batch <= 0 || batch > 65535 || side < 4 || !vv_is_pow2(side) || cin != FL_CIN) return VV_ERR_SHAPE;
     if (dtype == VV_FP8 && side < 8) return VV_ERR_SHAPE;                  // the e4m3fn input exists in sweep form only
     if (!vv_aligned16(x) || !vv_aligned16(target) || (probs && !vv_aligned16(probs)) || (logits && !vv_aligned16(logits)))

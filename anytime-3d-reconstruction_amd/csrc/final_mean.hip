@@ -259,15 +259,16 @@ size_t fm_partials_bytes(int objects, int side) { return (size_t)objects * ((8 *
 VV_EXPORT int vv_sample_latents(const float *mean, const float *logvar, const float *eps, float *z, void *z_act, int act_dtype, int objects,
                                 int samples, int latent, void *stream) {
     if (!mean || !logvar || !eps || (!z && !z_act)) return VV_ERR_NULL;
-    if (z_act && act_dtype != VV_F32 && act_dtype != VV_BF16) return VV_ERR_DTYPE;
+    if (z_act && !vv_dtype_in<float, __bf16>(act_dtype)) return VV_ERR_DTYPE;
     if (objects <= 0 || samples <= 0 || latent <= 0) return VV_ERR_SHAPE;
     const long total = (long)objects * samples * latent;
     const dim3 grid((unsigned)((total + 255) / 256));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (act_dtype == VV_BF16)
-        VV_LAUNCH(sample_latents_kernel<__bf16>, grid, dim3(256), 0, st, mean, logvar, eps, z, reinterpret_cast<__bf16 *>(z_act), samples, latent, total);
-    else
-        VV_LAUNCH(sample_latents_kernel<float>, grid, dim3(256), 0, st, mean, logvar, eps, z, reinterpret_cast<float *>(z_act), samples, latent, total);
+    // without z_act act_dtype is not checked and nothing is stored as it: any code but VV_BF16 takes the float instantiation
+    vv_with_dtype<float, __bf16>(act_dtype == VV_BF16 ? VV_BF16 : VV_F32, [&](auto t) {
+        using T = typename decltype(t)::type;
+        VV_LAUNCH(sample_latents_kernel<T>, grid, dim3(256), 0, st, mean, logvar, eps, z, reinterpret_cast<T *>(z_act), samples, latent, total);
+    });
     return vv_launch_status();
 }
 
@@ -281,7 +282,7 @@ VV_EXPORT int vv_convT3d_final_mean_fwd(const void *x, const float *w_keras, con
                                         int samples, int side, int cin, float gamma, float epsilon, int dtype, void *workspace,
                                         size_t workspace_bytes, void *stream) {
     if (!x || !w_keras || !mean_probs || (target != nullptr) != (stats != nullptr)) return VV_ERR_NULL;
-    if (dtype != VV_F32 && dtype != VV_BF16) return VV_ERR_DTYPE;
+    if (!vv_dtype_in<float, __bf16>(dtype)) return VV_ERR_DTYPE;
     if (objects <= 0 || samples < 1 || samples > 1024 || (long)objects * samples > 65535 || side < 4 || !vv_is_pow2(side) || cin != FL_CIN)
         return VV_ERR_SHAPE;
     if (!vv_aligned16(x) || (target && !vv_aligned16(target)) || !vv_aligned16(mean_probs)) return VV_ERR_ALIGN;
@@ -316,13 +317,11 @@ VV_EXPORT int vv_convT3d_final_mean_fwd(const void *x, const float *w_keras, con
         }
     } else {
         const dim3 grid((unsigned)((side / 4) * (side / 4) * (side / 4)), (unsigned)(objects * p.nslices));
-        if (dtype == VV_BF16) {
-            vv_allow_lds<&final_mean_box_kernel<__bf16>>(FMB_LDS);
-            VV_LAUNCH(final_mean_box_kernel<__bf16>, grid, dim3(256), FMB_LDS, st, reinterpret_cast<const __bf16 *>(x), w_keras, a, vv_log2(side));
-        } else {
-            vv_allow_lds<&final_mean_box_kernel<float>>(FMB_LDS);
-            VV_LAUNCH(final_mean_box_kernel<float>, grid, dim3(256), FMB_LDS, st, reinterpret_cast<const float *>(x), w_keras, a, vv_log2(side));
-        }
+        vv_with_dtype<float, __bf16>(dtype, [&](auto t) {
+            using T = typename decltype(t)::type;
+            vv_allow_lds<&final_mean_box_kernel<T>>(FMB_LDS);
+            VV_LAUNCH(final_mean_box_kernel<T>, grid, dim3(256), FMB_LDS, st, reinterpret_cast<const T *>(x), w_keras, a, vv_log2(side));
+        });
     }
     VV_LAUNCH(final_mean_finish_kernel, dim3((unsigned)p.nfin, (unsigned)objects), dim3(256), 0, st, a, (int)vox);
     if (target) vv_final_reduce_launch(a.partials, stats, p.nfin, objects, st);

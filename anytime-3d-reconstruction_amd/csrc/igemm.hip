@@ -718,8 +718,7 @@ int run_igemm(int mode, const void *x, const void *w, const float *scale, const 
               int K, int din, int cin, int act, int dtype, int out_dtype, void *ws, size_t ws_bytes, void *stream,
               int batch = 1) {
     if (!x || !w || !y) return VV_ERR_NULL;
-    if (dtype != VV_F32 && dtype != VV_BF16 && dtype != VV_FP8) return VV_ERR_DTYPE;
-    if (out_dtype != VV_F32 && out_dtype != VV_BF16 && out_dtype != VV_FP8) return VV_ERR_DTYPE;
+    if (!vv_dtype_in<float, __bf16, vv_fp8>(dtype) || !vv_dtype_in<float, __bf16, vv_fp8>(out_dtype)) return VV_ERR_DTYPE;
     if (mode == MODE_FIRST && dtype == VV_FP8) return VV_ERR_DTYPE;
     if (dtype == VV_F32 && out_dtype == VV_FP8) return VV_ERR_DTYPE;          // fp8 activations come from the bf16 / fp8 MFMA paths
     const int bk = dtype == VV_BF16 ? 64 : (dtype == VV_FP8 ? 128 : 32);
@@ -756,20 +755,18 @@ int run_igemm(int mode, const void *x, const void *w, const float *scale, const 
     a.nparity = p.nparity;
     a.pos_major = use_pos_major(mode, din, batch);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (mode == MODE_FIRST) return dtype == VV_BF16 ? launch_t<__bf16, MODE_FIRST>(a, p, st) : launch_t<float, MODE_FIRST>(a, p, st);
-    if (dtype == VV_BF16) {
-        if (mode == MODE_DENSE) return launch_t<__bf16, MODE_DENSE>(a, p, st);
-        if (mode == MODE_CONV) return launch_t<__bf16, MODE_CONV>(a, p, st);
-        return launch_t<__bf16, MODE_CONVT>(a, p, st);
+    int status = VV_ERR_DTYPE;
+    if (mode == MODE_FIRST) {       // float32 and bf16 only (e4m3fn was refused above): there is no launch_t<vv_fp8, MODE_FIRST>
+        vv_with_dtype<float, __bf16>(dtype, [&](auto t) { status = launch_t<typename decltype(t)::type, MODE_FIRST>(a, p, st); });
+        return status;
     }
-    if (dtype == VV_FP8) {
-        if (mode == MODE_DENSE) return launch_t<vv_fp8, MODE_DENSE>(a, p, st);
-        if (mode == MODE_CONV) return launch_t<vv_fp8, MODE_CONV>(a, p, st);
-        return launch_t<vv_fp8, MODE_CONVT>(a, p, st);
-    }
-    if (mode == MODE_DENSE) return launch_t<float, MODE_DENSE>(a, p, st);
-    if (mode == MODE_CONV) return launch_t<float, MODE_CONV>(a, p, st);
-    return launch_t<float, MODE_CONVT>(a, p, st);
+    vv_with_dtype<float, __bf16, vv_fp8>(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (mode == MODE_DENSE) status = launch_t<T, MODE_DENSE>(a, p, st);
+        else if (mode == MODE_CONV) status = launch_t<T, MODE_CONV>(a, p, st);
+        else status = launch_t<T, MODE_CONVT>(a, p, st);
+    });
+    return status;
 }
 
 }  // namespace

@@ -177,16 +177,13 @@ VV_EXPORT int vv_latent_mask_fill(const float *z, const float *mask, const float
                                   void *z_act, int act_dtype, int batch, int latent, void *stream) {
     if (!z || !mask || !prototypes || !z_out) return VV_ERR_NULL;
     if (batch <= 0 || latent <= 0 || classes <= 0) return VV_ERR_SHAPE;
-    if (z_act && act_dtype != VV_F32 && act_dtype != VV_BF16) return VV_ERR_DTYPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((batch * latent + 255) / 256), block(256);
-    if (z_act && act_dtype == VV_BF16)
-        VV_LAUNCH((mask_fill_kernel<__bf16>), grid, block, 0, st, z, mask, prototypes, classes, z_out,
-                           reinterpret_cast<__bf16 *>(z_act), batch, latent);
-    else
-        VV_LAUNCH((mask_fill_kernel<float>), grid, block, 0, st, z, mask, prototypes, classes, z_out,
-                           reinterpret_cast<float *>(z_act), batch, latent);
-    return vv_launch_status();
+    const bool ok = vv_with_dtype<float, __bf16>(z_act ? act_dtype : VV_F32, [&](auto t) {       // without z_act act_dtype is not read
+        using T = typename decltype(t)::type;
+        VV_LAUNCH(mask_fill_kernel<T>, grid, block, 0, st, z, mask, prototypes, classes, z_out, reinterpret_cast<T *>(z_act), batch, latent);
+    });
+    return ok ? vv_launch_status() : VV_ERR_DTYPE;
 }
 
 VV_EXPORT int vv_nearest_category(const float *z, const float *mask, const float *prototypes, int classes, int *argmin,
@@ -202,16 +199,13 @@ VV_EXPORT int vv_latent_correct(const float *z, const float *mask, const float *
                                 float *z_corr, void *z_act, int act_dtype, int batch, int latent, void *stream) {
     if (!z || !mask || !prototypes || !argmin || !eps2 || !z_corr) return VV_ERR_NULL;
     if (batch <= 0 || latent <= 0) return VV_ERR_SHAPE;
-    if (z_act && act_dtype != VV_F32 && act_dtype != VV_BF16) return VV_ERR_DTYPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((batch * latent + 255) / 256), block(256);
-    if (z_act && act_dtype == VV_BF16)
-        VV_LAUNCH((latent_correct_kernel<__bf16>), grid, block, 0, st, z, mask, prototypes, argmin, eps2, z_corr,
-                           reinterpret_cast<__bf16 *>(z_act), batch, latent);
-    else
-        VV_LAUNCH((latent_correct_kernel<float>), grid, block, 0, st, z, mask, prototypes, argmin, eps2, z_corr,
-                           reinterpret_cast<float *>(z_act), batch, latent);
-    return vv_launch_status();
+    const bool ok = vv_with_dtype<float, __bf16>(z_act ? act_dtype : VV_F32, [&](auto t) {       // without z_act act_dtype is not read
+        using T = typename decltype(t)::type;
+        VV_LAUNCH(latent_correct_kernel<T>, grid, block, 0, st, z, mask, prototypes, argmin, eps2, z_corr, reinterpret_cast<T *>(z_act), batch, latent);
+    });
+    return ok ? vv_launch_status() : VV_ERR_DTYPE;
 }
 
 VV_EXPORT int vv_category_accuracy(const int *argmin, const float *onehot, int classes, float *acc, int batch, void *stream) {

@@ -154,7 +154,7 @@ int mm_eval_check(const VvMmEval &a) {
     if ((a.mask != nullptr) != (a.eps2 != nullptr)) return VV_ERR_NULL;        // eps2 exactly when the mask is given
     if (a.mask && !a.z_corr) return VV_ERR_NULL;
     if (!mm_dims_ok(a.B, a.Lc, a.Li) || !mm_count_ok(a.C) || !mm_count_ok(a.I)) return VV_ERR_SHAPE;
-    if ((a.z_act || a.z_corr_act) && a.act_dtype != VV_F32 && a.act_dtype != VV_BF16) return VV_ERR_DTYPE;
+    if ((a.z_act || a.z_corr_act) && !vv_dtype_in<float, __bf16>(a.act_dtype)) return VV_ERR_DTYPE;
     const void *f32s[] = {a.enc_out, a.eps, a.mask, a.eps2, a.prior_cat, a.prior_inst, a.cat_onehot, a.inst_onehot, a.z, a.z_corr, a.idx, a.acc};
     for (const void *p : f32s)
         if (mm_misaligned(p, 3u)) return VV_ERR_ALIGN;
@@ -169,7 +169,7 @@ int mm_train_check(const VvMmTrain &a, bool bwd) {
         if (!p) return VV_ERR_NULL;
     if (bwd ? (!a.dz_in || !a.d_enc_out) : (!a.z_in || !a.kl || !a.reg)) return VV_ERR_NULL;
     if (!mm_dims_ok(a.B, a.Lc, a.Li) || !mm_count_ok(a.C)) return VV_ERR_SHAPE;
-    if (!bwd && a.z_in_act && a.act_dtype != VV_F32 && a.act_dtype != VV_BF16) return VV_ERR_DTYPE;
+    if (!bwd && a.z_in_act && !vv_dtype_in<float, __bf16>(a.act_dtype)) return VV_ERR_DTYPE;
     const void *f32s[] = {a.enc_out, a.eps, a.mean_cp, a.lv_cp, a.mean_ip, a.lv_ip, a.eps_p, a.noise, a.cat_onehot, a.dz_in, a.z_in, a.kl, a.reg,
                           a.d_enc_out, a.d_mean_cp, a.d_lv_cp, a.d_mean_ip, a.d_lv_ip};
     for (const void *p : f32s)

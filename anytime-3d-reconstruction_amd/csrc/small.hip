@@ -319,24 +319,19 @@ __global__ void convert_bf16_fp8_kernel(const bf16x8 *__restrict__ src, u32x2 *_
     }
 }
 
-}  // namespace
+// The element-wise packers, one thread per element of the packed image: kernel(vv_type<T>{}) is the instantiation for element type T,
+// launched over `total` elements with (w_keras, (T *)packed, shape...).
+template <typename Kernel, typename... Shape>
+int pack_launch(Kernel kernel, size_t total, const float *w_keras, void *packed, int dtype, void *stream, Shape... shape) {
+    if (!w_keras || !packed) return VV_ERR_NULL;
+    const bool ok = vv_with_dtype<float, __bf16, vv_fp8>(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        VV_LAUNCH(kernel(t), dim3(vv_grid_1d(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_keras, reinterpret_cast<T *>(packed), shape...);
+    });
+    return ok ? vv_launch_status() : VV_ERR_DTYPE;
+}
 
-#define VV_PACK_DISPATCH(KERNEL, TOTAL, ...)                                                                   \
-    do {                                                                                                       \
-        if (!w_keras || !packed) return VV_ERR_NULL;                                                           \
-        if (dtype != VV_F32 && dtype != VV_BF16 && dtype != VV_FP8) return VV_ERR_DTYPE;                       \
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);                                                \
-        if (dtype == VV_BF16)                                                                                  \
-            VV_LAUNCH((KERNEL<__bf16>), dim3(vv_grid_1d(TOTAL)), dim3(256), 0, st, w_keras,                    \
-                               reinterpret_cast<__bf16 *>(packed), __VA_ARGS__);                               \
-        else if (dtype == VV_FP8)                                                                              \
-            VV_LAUNCH((KERNEL<vv_fp8>), dim3(vv_grid_1d(TOTAL)), dim3(256), 0, st, w_keras,                    \
-                               reinterpret_cast<vv_fp8 *>(packed), __VA_ARGS__);                               \
-        else                                                                                                   \
-            VV_LAUNCH((KERNEL<float>), dim3(vv_grid_1d(TOTAL)), dim3(256), 0, st, w_keras,                     \
-                               reinterpret_cast<float *>(packed), __VA_ARGS__);                                \
-        return vv_launch_status();                                                                             \
-    } while (0)
+}  // namespace
 
 thread_local int vv_tls_last_hip_error = 0;
 
@@ -359,41 +354,43 @@ VV_EXPORT const char *vv_status_string(int s) {
 
 VV_EXPORT int vv_pack_conv_k4(const float *w_keras, void *packed, int cin, int cout, int dtype, void *stream) {
     if (cin <= 0 || cout <= 0) return VV_ERR_SHAPE;
-    if (w_keras && packed && cout % 64 == 0 && (dtype == VV_F32 || dtype == VV_BF16 || dtype == VV_FP8) && vv_aligned16(w_keras) && vv_aligned16(packed)) {
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (w_keras && packed && cout % 64 == 0 && vv_aligned16(w_keras) && vv_aligned16(packed)) {
         const dim3 grid(cin, cout / 64);                 // K / 64 = cin
-        if (dtype == VV_FP8) VV_LAUNCH(pack_conv_k4_tiled_kernel<vv_fp8>, grid, dim3(256), 0, st, w_keras, reinterpret_cast<vv_fp8 *>(packed), cin, cout);
-        else if (dtype == VV_BF16) VV_LAUNCH(pack_conv_k4_tiled_kernel<__bf16>, grid, dim3(256), 0, st, w_keras, reinterpret_cast<__bf16 *>(packed), cin, cout);
-        else VV_LAUNCH(pack_conv_k4_tiled_kernel<float>, grid, dim3(256), 0, st, w_keras, reinterpret_cast<float *>(packed), cin, cout);
-        return vv_launch_status();
+        const bool tiled = vv_with_dtype<float, __bf16, vv_fp8>(dtype, [&](auto t) {
+            using T = typename decltype(t)::type;
+            VV_LAUNCH(pack_conv_k4_tiled_kernel<T>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_keras, reinterpret_cast<T *>(packed), cin, cout);
+        });
+        if (tiled) return vv_launch_status();
     }
-    VV_PACK_DISPATCH(pack_conv_k4_kernel, (size_t)64 * cin * cout, cin, cout);
+    return pack_launch([](auto t) { return pack_conv_k4_kernel<typename decltype(t)::type>; }, (size_t)64 * cin * cout, w_keras, packed, dtype, stream, cin, cout);
 }
 
 VV_EXPORT int vv_pack_convT_k4s2(const float *w_keras, void *packed, int cin, int cout, int dtype, void *stream) {
     if (cin <= 0 || cout <= 0) return VV_ERR_SHAPE;
     if (cin % 4 == 0 && vv_aligned16(w_keras) && vv_aligned16(packed))
-        VV_PACK_DISPATCH(pack_convT_k4s2_vec_kernel, (size_t)16 * cin * cout, cin, cout);
-    VV_PACK_DISPATCH(pack_convT_k4s2_kernel, (size_t)64 * cin * cout, cin, cout);
+        return pack_launch([](auto t) { return pack_convT_k4s2_vec_kernel<typename decltype(t)::type>; }, (size_t)16 * cin * cout, w_keras, packed, dtype, stream, cin, cout);
+    return pack_launch([](auto t) { return pack_convT_k4s2_kernel<typename decltype(t)::type>; }, (size_t)64 * cin * cout, w_keras, packed, dtype, stream, cin, cout);
 }
 
 VV_EXPORT int vv_pack_conv_k4s1_meanpool(const float *w_keras, void *packed, int side, int cin, int cout, int dtype,
                                          void *stream) {
     if (cin <= 0 || cout <= 0 || side <= 0) return VV_ERR_SHAPE;
-    if (w_keras && packed && cin % 64 == 0 && cout % 64 == 0 && (dtype == VV_F32 || dtype == VV_BF16) && vv_aligned16(w_keras)) {
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (w_keras && packed && cin % 64 == 0 && cout % 64 == 0 && vv_aligned16(w_keras)) {
         const dim3 grid(side * side * side * (cin / 64), cout / 64);
-        if (dtype == VV_BF16) VV_LAUNCH(pack_conv_k4s1_meanpool_tiled_kernel<__bf16>, grid, dim3(256), 0, st, w_keras, reinterpret_cast<__bf16 *>(packed), side, cin, cout);
-        else VV_LAUNCH(pack_conv_k4s1_meanpool_tiled_kernel<float>, grid, dim3(256), 0, st, w_keras, reinterpret_cast<float *>(packed), side, cin, cout);
-        return vv_launch_status();
+        const bool tiled = vv_with_dtype<float, __bf16>(dtype, [&](auto t) {      // e4m3fn images take the element-wise kernel below
+            using T = typename decltype(t)::type;
+            VV_LAUNCH(pack_conv_k4s1_meanpool_tiled_kernel<T>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_keras, reinterpret_cast<T *>(packed), side, cin, cout);
+        });
+        if (tiled) return vv_launch_status();
     }
-    VV_PACK_DISPATCH(pack_conv_k4s1_meanpool_kernel, (size_t)side * side * side * cin * cout, side, cin, cout);
+    return pack_launch([](auto t) { return pack_conv_k4s1_meanpool_kernel<typename decltype(t)::type>; }, (size_t)side * side * side * cin * cout, w_keras, packed,
+                       dtype, stream, side, cin, cout);
 }
 
 VV_EXPORT int vv_pack_conv_k4s1_full(const float *w_keras, void *packed, int side, int cin, int cout, int dtype, void *stream) {
     if (cin <= 0 || cout <= 0 || side <= 0) return VV_ERR_SHAPE;
     const size_t s3 = (size_t)side * side * side;
-    VV_PACK_DISPATCH(pack_conv_k4s1_full_kernel, s3 * cout * s3 * cin, side, cin, cout);
+    return pack_launch([](auto t) { return pack_conv_k4s1_full_kernel<typename decltype(t)::type>; }, s3 * cout * s3 * cin, w_keras, packed, dtype, stream, side, cin, cout);
 }
 
 VV_EXPORT int vv_sigmoid_f32(const float *x, float *y, long n, void *stream) {
@@ -415,12 +412,12 @@ VV_EXPORT int vv_pack_convT_k4s1_dense(const float *w_keras, void *packed, int s
                                        void *stream) {
     if (cin <= 0 || cout <= 0 || side <= 0) return VV_ERR_SHAPE;
     const size_t s3 = (size_t)side * side * side;
-    VV_PACK_DISPATCH(pack_convT_k4s1_dense_kernel, s3 * cout * s3 * cin, side, cin, cout);
+    return pack_launch([](auto t) { return pack_convT_k4s1_dense_kernel<typename decltype(t)::type>; }, s3 * cout * s3 * cin, w_keras, packed, dtype, stream, side, cin, cout);
 }
 
 VV_EXPORT int vv_pack_dense(const float *w_keras, void *packed, int in, int out, int dtype, void *stream) {
     if (in <= 0 || out <= 0) return VV_ERR_SHAPE;
-    VV_PACK_DISPATCH(pack_dense_kernel, (size_t)in * out, in, out);
+    return pack_launch([](auto t) { return pack_dense_kernel<typename decltype(t)::type>; }, (size_t)in * out, w_keras, packed, dtype, stream, in, out);
 }
 
 VV_EXPORT int vv_fold_bn(const float *gamma, const float *beta, const float *mean, const float *var, const float *bias,
@@ -438,16 +435,13 @@ VV_EXPORT int vv_reparam_kl_fwd(const float *enc_out, const float *eps, const fl
                                 void *stream) {
     if (!enc_out || !eps || !z) return VV_ERR_NULL;
     if (batch <= 0 || latent <= 0) return VV_ERR_SHAPE;
-    if (z_act && act_dtype != VV_F32 && act_dtype != VV_BF16) return VV_ERR_DTYPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((batch + 3) / 4), block(256);
-    if (z_act && act_dtype == VV_BF16)
-        VV_LAUNCH((reparam_kl_kernel<__bf16>), grid, block, 0, st, enc_out, eps, drop_mask, drop_scale, z,
-                           reinterpret_cast<__bf16 *>(z_act), kl, mean, logvar, batch, latent);
-    else
-        VV_LAUNCH((reparam_kl_kernel<float>), grid, block, 0, st, enc_out, eps, drop_mask, drop_scale, z,
-                           reinterpret_cast<float *>(z_act), kl, mean, logvar, batch, latent);
-    return vv_launch_status();
+    const bool ok = vv_with_dtype<float, __bf16>(z_act ? act_dtype : VV_F32, [&](auto t) {       // without z_act act_dtype is not read
+        using T = typename decltype(t)::type;
+        VV_LAUNCH(reparam_kl_kernel<T>, grid, block, 0, st, enc_out, eps, drop_mask, drop_scale, z, reinterpret_cast<T *>(z_act), kl, mean, logvar, batch, latent);
+    });
+    return ok ? vv_launch_status() : VV_ERR_DTYPE;
 }
 
 void vv_shape_metrics_launch(const float *stats, float *out4, int batch, hipStream_t st) {
@@ -482,30 +476,24 @@ VV_EXPORT int vv_pack_bits(const float *x, void *packed, float threshold, long n
 
 VV_EXPORT int vv_convert(const void *src, void *dst, long n, int src_dtype, int dst_dtype, void *stream) {
     if (!src || !dst) return VV_ERR_NULL;
-    if (src_dtype != VV_F32 && src_dtype != VV_BF16 && src_dtype != VV_FP8) return VV_ERR_DTYPE;
-    if (dst_dtype != VV_F32 && dst_dtype != VV_BF16 && dst_dtype != VV_FP8) return VV_ERR_DTYPE;
+    if (!vv_dtype_in<float, __bf16, vv_fp8>(src_dtype) || !vv_dtype_in<float, __bf16, vv_fp8>(dst_dtype)) return VV_ERR_DTYPE;
     if (n <= 0) return VV_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 g(vv_grid_1d((size_t)n)), b(256);
-    if (src_dtype == VV_BF16 && dst_dtype == VV_FP8 && n % 8 == 0 && vv_aligned16(src) && vv_aligned16(dst))
+    if (src_dtype == VV_BF16 && dst_dtype == VV_FP8 && n % 8 == 0 && vv_aligned16(src) && vv_aligned16(dst)) {
         VV_LAUNCH(convert_bf16_fp8_kernel, dim3(vv_grid_1d((size_t)(n / 8))), b, 0, st, reinterpret_cast<const bf16x8 *>(src), reinterpret_cast<u32x2 *>(dst), n / 8);
-    else if (dst_dtype == VV_FP8 && src_dtype == VV_F32)
-        VV_LAUNCH((convert_kernel<float, vv_fp8>), g, b, 0, st, reinterpret_cast<const float *>(src), reinterpret_cast<vv_fp8 *>(dst), n);
-    else if (dst_dtype == VV_FP8 && src_dtype == VV_BF16)
-        VV_LAUNCH((convert_kernel<__bf16, vv_fp8>), g, b, 0, st, reinterpret_cast<const __bf16 *>(src), reinterpret_cast<vv_fp8 *>(dst), n);
-    else if (src_dtype == VV_FP8 && dst_dtype == VV_F32)
-        VV_LAUNCH((convert_kernel<vv_fp8, float>), g, b, 0, st, reinterpret_cast<const vv_fp8 *>(src), reinterpret_cast<float *>(dst), n);
-    else if (src_dtype == VV_FP8 && dst_dtype == VV_BF16)
-        VV_LAUNCH((convert_kernel<vv_fp8, __bf16>), g, b, 0, st, reinterpret_cast<const vv_fp8 *>(src), reinterpret_cast<__bf16 *>(dst), n);
-    else if (src_dtype == VV_FP8)
-        return VV_ERR_DTYPE;
-    else if (src_dtype == VV_F32 && dst_dtype == VV_BF16)
-        VV_LAUNCH((convert_kernel<float, __bf16>), g, b, 0, st, reinterpret_cast<const float *>(src), reinterpret_cast<__bf16 *>(dst), n);
-    else if (src_dtype == VV_BF16 && dst_dtype == VV_F32)
-        VV_LAUNCH((convert_kernel<__bf16, float>), g, b, 0, st, reinterpret_cast<const __bf16 *>(src), reinterpret_cast<float *>(dst), n);
-    else if (src_dtype == VV_F32)
-        VV_LAUNCH((convert_kernel<float, float>), g, b, 0, st, reinterpret_cast<const float *>(src), reinterpret_cast<float *>(dst), n);
-    else
-        VV_LAUNCH((convert_kernel<__bf16, __bf16>), g, b, 0, st, reinterpret_cast<const __bf16 *>(src), reinterpret_cast<__bf16 *>(dst), n);
-    return vv_launch_status();
+        return vv_launch_status();
+    }
+    bool ok = false;
+    vv_with_dtype<float, __bf16, vv_fp8>(src_dtype, [&](auto s) {
+        using TS = typename decltype(s)::type;
+        const auto launch = [&](auto d) {
+            using TD = typename decltype(d)::type;
+            VV_LAUNCH((convert_kernel<TS, TD>), g, b, 0, st, reinterpret_cast<const TS *>(src), reinterpret_cast<TD *>(dst), n);
+        };
+        // e4m3fn to e4m3fn is no conversion and has no kernel: the one pair of admitted codes that is refused
+        if constexpr (std::is_same<TS, vv_fp8>::value) ok = vv_with_dtype<float, __bf16>(dst_dtype, launch);
+        else ok = vv_with_dtype<float, __bf16, vv_fp8>(dst_dtype, launch);
+    });
+    return ok ? vv_launch_status() : VV_ERR_DTYPE;
 }

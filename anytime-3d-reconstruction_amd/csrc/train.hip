@@ -901,19 +901,18 @@ VV_EXPORT int vv_bn_train_stats(const void *x, long rows, int channels, const fl
                                 float momentum, float *mean, float *var, float *rstd, float *scale, float *shift,
                                 float *moving_mean, float *moving_var, int dtype, void *workspace, size_t workspace_bytes, void *stream) {
     if (!x || !gamma || !beta || !mean || !var || !rstd || !scale || !shift) return VV_ERR_NULL;
-    if (dtype != VV_F32 && dtype != VV_BF16) return VV_ERR_DTYPE;
+    if (!vv_dtype_in<float, __bf16>(dtype)) return VV_ERR_DTYPE;
     if (!bn_shape_ok(rows, channels, dtype)) return VV_ERR_SHAPE;
     if (!workspace || workspace_bytes < vv_bn_workspace_bytes(rows, channels)) return VV_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nb = bn_blocks(rows, channels, dtype == VV_BF16 ? 8 : 4);     // <= the float32 count the workspace is sized for
     const int rpb = (int)((rows + nb - 1) / nb);
     float *part = reinterpret_cast<float *>(workspace);
-    if (dtype == VV_BF16)
-        VV_LAUNCH((bn_reduce_kernel<0, __bf16>), dim3(nb), dim3(256), 0, st, reinterpret_cast<const __bf16 *>(x), nullptr, nullptr, nullptr,
-                  nullptr, nullptr, part, rows, channels, rpb, 0);
-    else
-        VV_LAUNCH((bn_reduce_kernel<0, float>), dim3(nb), dim3(256), 0, st, reinterpret_cast<const float *>(x), nullptr, nullptr, nullptr,
-                  nullptr, nullptr, part, rows, channels, rpb, 0);
+    vv_with_dtype<float, __bf16>(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        VV_LAUNCH((bn_reduce_kernel<0, T>), dim3(nb), dim3(256), 0, st, reinterpret_cast<const T *>(x), nullptr, nullptr, nullptr, nullptr, nullptr, part,
+                  rows, channels, rpb, 0);
+    });
     VV_LAUNCH(bn_stats_finalize_kernel, dim3((channels + BN_FC - 1) / BN_FC), dim3(256), 0, st, part, nb, rows, channels, gamma, beta, eps,
               momentum, mean, var, rstd, scale, shift, moving_mean, moving_var);
     return vv_launch_status();
@@ -934,16 +933,14 @@ VV_EXPORT int vv_bn_finalize_stats(const float *partial, int nblocks, long rows,
 VV_EXPORT int vv_bn_act_fwd(const void *x, const float *scale, const float *shift, void *y, long rows, int channels, int act,
                             int dtype, void *stream) {
     if (!x || !scale || !shift || !y) return VV_ERR_NULL;
-    if (dtype != VV_F32 && dtype != VV_BF16) return VV_ERR_DTYPE;
+    if (!vv_dtype_in<float, __bf16>(dtype)) return VV_ERR_DTYPE;
     if (!bn_shape_ok(rows, channels, dtype)) return VV_ERR_SHAPE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int grid = bn_sweep_blocks(rows, channels, dtype == VV_BF16 ? 8 : 4);
-    if (dtype == VV_BF16)
-        VV_LAUNCH(bn_act_fwd_kernel<__bf16>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const __bf16 *>(x), scale, shift,
-                  reinterpret_cast<__bf16 *>(y), rows, channels, act);
-    else
-        VV_LAUNCH(bn_act_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const float *>(x), scale, shift,
-                  reinterpret_cast<float *>(y), rows, channels, act);
+    vv_with_dtype<float, __bf16>(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        VV_LAUNCH(bn_act_fwd_kernel<T>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const T *>(x), scale, shift, reinterpret_cast<T *>(y), rows, channels, act);
+    });
     return vv_launch_status();
 }
 
@@ -951,7 +948,7 @@ VV_EXPORT int vv_bn_act_bwd(const void *x, const void *dy, const float *scale, c
                             const float *rstd, float *dgamma, float *dbeta, void *dx, long rows, int channels, int act,
                             int dtype, void *workspace, size_t workspace_bytes, void *stream) {
     if (!x || !dy || !scale || !shift || !mean || !rstd || !dgamma || !dbeta || !dx) return VV_ERR_NULL;
-    if (dtype != VV_F32 && dtype != VV_BF16) return VV_ERR_DTYPE;
+    if (!vv_dtype_in<float, __bf16>(dtype)) return VV_ERR_DTYPE;
     if (!bn_shape_ok(rows, channels, dtype)) return VV_ERR_SHAPE;
     if (!workspace || workspace_bytes < vv_bn_workspace_bytes(rows, channels)) return VV_ERR_WORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -959,20 +956,17 @@ VV_EXPORT int vv_bn_act_bwd(const void *x, const void *dy, const float *scale, c
     const int rpb = (int)((rows + nb - 1) / nb);
     float *part = reinterpret_cast<float *>(workspace);
     const int sweep = bn_sweep_blocks(rows, channels, dtype == VV_BF16 ? 8 : 4);
-    if (dtype == VV_BF16) {
-        const __bf16 *xb = reinterpret_cast<const __bf16 *>(x), *dyb = reinterpret_cast<const __bf16 *>(dy);
-        if (act == VV_ACT_ELU) VV_LAUNCH((bn_reduce_kernel<1, __bf16, VV_ACT_ELU>), dim3(nb), dim3(256), 0, st, xb, dyb, scale, shift, mean, rstd, part, rows, channels, rpb, act);
-        else VV_LAUNCH((bn_reduce_kernel<1, __bf16>), dim3(nb), dim3(256), 0, st, xb, dyb, scale, shift, mean, rstd, part, rows, channels, rpb, act);
+    vv_with_dtype<float, __bf16>(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        const T *xt = reinterpret_cast<const T *>(x), *dyt = reinterpret_cast<const T *>(dy);
+        // the reduction with ELU as a compile-time constant exists for bf16 only; for float32 this is -1, the run-time switch itself
+        constexpr int ELU = std::is_same<T, __bf16>::value ? (int)VV_ACT_ELU : -1;
+        if (act == ELU) VV_LAUNCH((bn_reduce_kernel<1, T, ELU>), dim3(nb), dim3(256), 0, st, xt, dyt, scale, shift, mean, rstd, part, rows, channels, rpb, act);
+        else VV_LAUNCH((bn_reduce_kernel<1, T>), dim3(nb), dim3(256), 0, st, xt, dyt, scale, shift, mean, rstd, part, rows, channels, rpb, act);
         VV_LAUNCH(bn_bwd_finalize_kernel, dim3((channels + BN_FC - 1) / BN_FC), dim3(256), 0, st, part, nb, channels, dgamma, dbeta);
-        VV_LAUNCH(bn_act_bwd_kernel<__bf16>, dim3(sweep), dim3(256), 0, st, xb, dyb, scale, shift, mean, rstd, dgamma, dbeta,
-                  reinterpret_cast<__bf16 *>(dx), rows, channels, 1.0f / (float)rows, act);
-    } else {
-        const float *xf = reinterpret_cast<const float *>(x), *dyf = reinterpret_cast<const float *>(dy);
-        VV_LAUNCH((bn_reduce_kernel<1, float>), dim3(nb), dim3(256), 0, st, xf, dyf, scale, shift, mean, rstd, part, rows, channels, rpb, act);
-        VV_LAUNCH(bn_bwd_finalize_kernel, dim3((channels + BN_FC - 1) / BN_FC), dim3(256), 0, st, part, nb, channels, dgamma, dbeta);
-        VV_LAUNCH(bn_act_bwd_kernel<float>, dim3(sweep), dim3(256), 0, st, xf, dyf, scale, shift, mean, rstd, dgamma, dbeta,
-                  reinterpret_cast<float *>(dx), rows, channels, 1.0f / (float)rows, act);
-    }
+        VV_LAUNCH(bn_act_bwd_kernel<T>, dim3(sweep), dim3(256), 0, st, xt, dyt, scale, shift, mean, rstd, dgamma, dbeta, reinterpret_cast<T *>(dx), rows,
+                  channels, 1.0f / (float)rows, act);
+    });
     return vv_launch_status();
 }
 
@@ -1059,7 +1053,7 @@ VV_EXPORT size_t vv_wgrad_workspace_bytes(long rows, int m, int n) {
 VV_EXPORT int vv_wgrad_dense(const void *a, const void *g, float *dw, long rows, int m, int n, int lda, int a_dtype, int g_dtype,
                              void *workspace, size_t workspace_bytes, void *stream) {
     if (!a || !g || !dw) return VV_ERR_NULL;
-    if ((a_dtype != VV_F32 && a_dtype != VV_BF16) || (g_dtype != VV_F32 && g_dtype != VV_BF16)) return VV_ERR_DTYPE;
+    if (!vv_dtype_in<float, __bf16>(a_dtype) || !vv_dtype_in<float, __bf16>(g_dtype)) return VV_ERR_DTYPE;
     if (rows <= 0 || m <= 0 || n <= 0 || m % 4 || n % 4 || lda % 4) return VV_ERR_SHAPE;
     if (!workspace || workspace_bytes < vv_wgrad_workspace_bytes(rows, m, n)) return VV_ERR_WORKSPACE;
     if (a_dtype == VV_BF16 && g_dtype == VV_BF16 && wgrad_bf16_ok(a, g, rows, m, n, lda, 0, 0, (size_t)rows * lda)) {
@@ -1076,7 +1070,7 @@ VV_EXPORT int vv_wgrad_dense(const void *a, const void *g, float *dw, long rows,
 VV_EXPORT int vv_wgrad_conv_k4s2(const void *src, const void *g, float *dw, int batch, int side, int cin, int cout, int src_dtype,
                                  int g_dtype, void *workspace, size_t workspace_bytes, void *stream) {
     if (!src || !g || !dw) return VV_ERR_NULL;
-    if ((src_dtype != VV_F32 && src_dtype != VV_BF16) || (g_dtype != VV_F32 && g_dtype != VV_BF16)) return VV_ERR_DTYPE;
+    if (!vv_dtype_in<float, __bf16>(src_dtype) || !vv_dtype_in<float, __bf16>(g_dtype)) return VV_ERR_DTYPE;
     if (cin == 1 && src_dtype != VV_F32) return VV_ERR_DTYPE;               // single-channel sources are float32 grids
     if (batch <= 0 || side < 2 || !vv_is_pow2(side) || cout % 4 || (cin != 1 && cin % 64)) return VV_ERR_SHAPE;
     const int o = side / 2;
@@ -1176,10 +1170,11 @@ VV_EXPORT int vv_adam_step_multi(const void *chunk_table, int nchunks, float lr_
 
 VV_EXPORT int vv_colsum(const void *x, float *out, long rows, int cols, int dtype, void *stream) {
     if (!x || !out) return VV_ERR_NULL;
-    if (dtype != VV_F32 && dtype != VV_BF16) return VV_ERR_DTYPE;
+    if (!vv_dtype_in<float, __bf16>(dtype)) return VV_ERR_DTYPE;
     if (rows <= 0 || cols <= 0) return VV_ERR_SHAPE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == VV_BF16) VV_LAUNCH(colsum_kernel<__bf16>, dim3((cols + 31) / 32), dim3(256), 0, st, reinterpret_cast<const __bf16 *>(x), out, rows, cols);
-    else VV_LAUNCH(colsum_kernel<float>, dim3((cols + 31) / 32), dim3(256), 0, st, reinterpret_cast<const float *>(x), out, rows, cols);
+    vv_with_dtype<float, __bf16>(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        VV_LAUNCH(colsum_kernel<T>, dim3((cols + 31) / 32), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const T *>(x), out, rows, cols);
+    });
     return vv_launch_status();
 }
