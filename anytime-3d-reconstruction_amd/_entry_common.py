@@ -164,8 +164,10 @@ class RunningMeans:
 class Progress:
     """One carriage-return status line: iteration, mean step time, epoch, loader position, then labelled groups."""
 
-    def __init__(self, width=4):
-        self.pos_fmt = "cur_o/tot_o:{:0%dd}/{:0%dd} " % (width, width)
+    def __init__(self, width=4, head_fmt="it:{it:04d} rt:{rt:.2f} Ep_o:{ep:03d} ", pos_label="cur_o/tot_o"):
+        """head_fmt / pos_label: the names a script's reference prints for iteration, mean step time, epoch and loader position."""
+        self.head_fmt = head_fmt
+        self.pos_fmt = pos_label + ":{:0%dd}/{:0%dd} " % (width, width)
         self.elapsed, self.n = 0.0, 0
         self._t0 = None
 
@@ -184,23 +186,24 @@ class Progress:
         return sep.join("%s:%.4f" % (k, v) for k, v in pairs)
 
     def show(self, epoch, position, total, *groups):
-        head = "it:{:04d} rt:{:.2f} Ep_o:{:03d} ".format(self.n, self.elapsed / max(self.n, 1), int(epoch) + 1)
+        head = self.head_fmt.format(it=self.n, rt=self.elapsed / max(self.n, 1), ep=int(epoch) + 1)
         if SAMPLED is not None and SAMPLED['n']:
             groups = groups + (self.group(zip(('sloss', 'spr', 'src'), SAMPLED['sums'] / SAMPLED['n'])),)
         sys.stdout.write(head + self.pos_fmt.format(position, total) + " ".join(groups) + "  \r")
         sys.stdout.flush()
 
 
-def epochs_of(loader, limit, position_attr, on_new_epoch=None):
+def epochs_of(loader, limit, position_attr, on_new_epoch=None, every=None):
     """Yields (epoch, position, total) before every batch until `limit` epochs have been served; calls `on_new_epoch()`
-    when the loader's epoch counter has advanced (the scripts save the model and restart their running means there)."""
-    epoch, first = loader.epoch, True
+    when the loader's epoch counter has advanced (the scripts save the model and restart their running means there) and,
+    with `every`, also after every `every` batches since it last did."""
+    epoch, since = loader.epoch, 0
     while loader.epoch < limit:
-        if loader.epoch != epoch and not first:
-            epoch = loader.epoch
+        if since and (loader.epoch != epoch or since == every):
+            epoch, since = loader.epoch, 0
             if on_new_epoch is not None:
                 on_new_epoch()
-        first = False
+        since += 1
         yield loader.epoch, getattr(loader, position_attr), loader.dataLength
 
 

@@ -111,7 +111,7 @@ class Model(object):
     def losses(self):
         """Keras `model.losses`: the l2(0.0005) terms of every kernel and of the Dense bias (autoencoder3D.py:29,44,60-61,
         88,131), one scalar per regularised variable.  The modelnet classes of the hot path never add them to their loss
-        (nolbo.py:1436); the image -> 3D model does (nolbo.py:819-823) and AE3D.py:82 (out of scope) does."""
+        (nolbo.py:1436); the image -> 3D model does (nolbo.py:819-823) and AE3D.py:82 does (src/module/AE3D.py: inside the optimiser launch)."""
         p = self._engine.params
         return [L2_REG * (p[k].float() ** 2).sum() for k in self._engine.param_shapes() if _regularised(k)]
 

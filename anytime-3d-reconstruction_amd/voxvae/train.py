@@ -28,6 +28,59 @@ def _st():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def group_size():
+    import torch.distributed as dist
+    return dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
+
+
+class ReplicaStrategy:
+    """What the data-parallel classes need of the reference's tf.distribute strategy (AE3D.py:38-40, train_modelnet_AE.py:47-48):
+    `num_replicas_in_sync` (the initialised process group's size, else 1) and a `scope()` that does nothing -- replicas are
+    processes here, one per GPU, and every one builds its own copy of the model."""
+
+    @property
+    def num_replicas_in_sync(self):
+        return group_size()
+
+    def scope(self):
+        import contextlib
+        return contextlib.nullcontext()
+
+
+# ---------------------------------------------------------------------------------------------- l2 folded into Adam (AE3D.fit)
+ADAM_L2_PLAN = np.dtype([('var', np.int64), ('offset', np.int64), ('n', np.int64), ('coef', np.float32)])
+
+
+def l2_regularised(name):
+    """The variables autoencoder3D.py:29,44,60-61,88,131 gives a regulariser: every kernel and the Dense bias (what _add_l2 adds to)."""
+    return name.endswith('/kernel') or name == 'dec/dense/bias'
+
+
+def adam_l2_plan(named_shapes, weight_l2, world=1, chunk=ADAM_CHUNK):
+    """The records of the optimiser's table (vv_adam_step_multi_l2; without the coefficient, vv_adam_step_multi) before pointers exist: (name, shape) pairs in table order -> one record
+    (variable index, element offset, elements <= chunk, coefficient) per chunk, every element of every variable in exactly one.
+    The coefficient is that of the SUMMED gradient: each replica's loss carries the unscaled weight_l2 * sum w^2 and the gradients
+    are summed across replicas (AE3D.py:82-87), so it is 2 * weight_l2 * world on the regularised variables and 0 on BatchNorm's."""
+    recs = []
+    for k, (name, shape) in enumerate(named_shapes):
+        n = int(np.prod([int(s) for s in shape], dtype=np.int64)) if len(shape) else 1
+        coef = 2.0 * float(weight_l2) * int(world) if l2_regularised(name) else 0.0
+        for off in range(0, n, chunk):
+            recs.append((k, off, min(chunk, n - off), coef))
+    return np.array(recs, dtype=ADAM_L2_PLAN)
+
+
+def adam_l2_table(plan, pointers):
+    """plan + per-variable (param, grad, m, v) device pointers -> the table as int64 [nchunks, 6]: the four pointers offset to the
+    chunk, n, and the float32 coefficient's bits in the low half of the last word (include/voxvae.h has the record)."""
+    ptr = np.asarray(pointers, dtype=np.int64).reshape(-1, 4)
+    t = np.empty((plan.shape[0], 6), dtype=np.int64)
+    t[:, :4] = ptr[plan['var']] + 4 * plan['offset'][:, None]
+    t[:, 4] = plan['n']
+    t[:, 5] = np.ascontiguousarray(plan['coef']).view(np.uint32).astype(np.int64)
+    return t
+
+
 class GradBuckets:
     """Flat gradient storage: every trainable tensor's gradient is a view into one of a few large float32
     buffers, so the cross-rank sum is a handful of large all-reduces (per-link-bound xGMI rings want few, big
@@ -209,8 +262,14 @@ class _BN:
 
 
 class Trainer:
-    def __init__(self, enc, dec, variational=True, learning_rate=1e-4, world_size=1, group=None, grad_wire=None):
-        """grad_wire: 'f32' (default) or 'bf16' -- what the gradient buckets put on the wire (GradBuckets); VOXVAE_GRAD_WIRE sets the default."""
+    def __init__(self, enc, dec, variational=True, learning_rate=1e-4, world_size=1, group=None, grad_wire=None, weight_l2=0.0):
+        """grad_wire: 'f32' (default) or 'bf16' -- what the gradient buckets put on the wire (GradBuckets); VOXVAE_GRAD_WIRE sets the default.
+        weight_l2: coefficient of the kernel / Dense-bias regulariser that EVERY replica adds unscaled to its loss (AE3D.py:82-84).  Above 0
+        the optimiser launch is vv_adam_step_multi_l2: the term enters behind the cross-rank sum (the buckets keep overlapping with the
+        backward pass) and the same pass leaves sum w^2 for step_scalars().  At 0 nothing differs from a Trainer without the argument."""
+        if weight_l2 < 0:
+            raise ValueError('weight_l2 must be >= 0, got %r' % (weight_l2,))
+        self.weight_l2 = float(weight_l2)
         if enc is not None and enc.dt != dec.dt:
             raise ValueError('encoder and decoder engines must share one activation dtype')
         if dec.fp8 or (enc is not None and enc.fp8):
@@ -266,6 +325,7 @@ class Trainer:
         self.wgrad_stream, self._side_used = None, False
         self._prepacked = {}       # (direction, weight pointer, cin, cout) -> the step's batched 'skip' images (_prepack)
         self._adam_ptrs = None
+        self._sumsq = None         # weight_l2 > 0: the per-chunk sum w^2 the last optimiser launch left
 
     def _begin(self, *engines, step=False):
         """Start of every entry point: the switches are read once, the engines packed without folded vectors (batch statistics); an
@@ -440,6 +500,19 @@ class Trainer:
         self._apply()
         return kl, stats, metrics
 
+    def step_scalars(self, stats):
+        """The per-replica tuple of AE3D.fit (AE3D.py:67-90) for the step that returned `stats` [B,4], as ONE float32 device tensor
+        (reg_loss = weight_l2 * sum w^2 at the weights the forward used, pred_loss = sum bce / GLOBAL batch, their sum, and TP, FP, FN
+        summed over this replica's samples / GLOBAL batch): one small launch over stats and the optimiser's partials.  The cross-rank SUM
+        of this tensor is what AE3D.distributed_fit reduces."""
+        if self.weight_l2 > 0 and self._sumsq is None:
+            raise ValueError('step_scalars() follows an optimisation step: no step has run yet')
+        B = stats.shape[0]
+        out = self._empty(6)
+        nchunks = 0 if self._sumsq is None else self._sumsq.numel()
+        L.call('vv_ae3d_step_scalars', L.ptr(stats), B, L.ptr(self._sumsq), nchunks, self.weight_l2, 1.0 / float(B * self.world), L.ptr(out), _st())
+        return out
+
     def _prepack(self):
         """Every 'skip' weight image (position-major, skip and whole-sample forms) the step will ask for and no engine holds (forward
         layers and data gradients: nine at the 32^3 model), packed by ONE vv_pack_skip_images call = two launches, instead of nine 5-8 us
@@ -491,6 +564,7 @@ class Trainer:
         encoder owned by the caller.  Trains the decoder and returns (loss_kl, stats, metrics, d total / d enc_out) so the
         caller can continue the backward pass through its own encoder.  l2: coefficient of the decoder's kernel / bias
         regularisers when the caller's loss includes them."""
+        self._refuse_second_l2(l2)
         self._begin(self.dec, step=True)
         overlap, self.overlap = self.overlap, self.overlap and l2 == 0      # the l2 terms are added before the cross-rank sum
         B = enc_out.shape[0]
@@ -501,12 +575,16 @@ class Trainer:
         self._apply()
         return kl, stats, metrics, de
 
+    def _refuse_second_l2(self, l2):
+        if l2 > 0 and self.weight_l2 > 0:
+            raise ValueError('this Trainer folds weight_l2 = %g into its optimiser launch: l2 = %g on top would regularise twice' % (self.weight_l2, l2))
+
     def _add_l2(self, l2):
         """+ sum(decoder.losses) in the total loss (nolbo.py:819-823): d/dw of l2 * sum(w^2)."""
         if l2 > 0:
             self._join_wgrad()
             for name, _ in self.order:
-                if name.endswith('/kernel') or name == 'dec/dense/bias':
+                if l2_regularised(name):
                     self._g(name).add_(self._p(name), alpha=2.0 * l2 / self.world)
 
     def step_decoder(self, z_in, y, z_act=None, l2=0.0):
@@ -514,6 +592,7 @@ class Trainer:
         :565-603): z_in float32 [B, L] is the decoder's input, z_act its activation-dtype copy when the caller has one (cast here
         otherwise).  Trains the decoder and returns (stats, metrics, d shape / d z_in), the gradient scaled by 1 / global batch: the
         decoder half of step_custom_latent with the l2 handling of step_from_latent."""
+        self._refuse_second_l2(l2)
         self._begin(self.dec, step=True)
         overlap, self.overlap = self.overlap, self.overlap and l2 == 0
         B = z_in.shape[0]
@@ -746,16 +825,16 @@ class Trainer:
         lr_t = self.lr * (1.0 - ADAM_B2 ** self.t) ** 0.5 / (1.0 - ADAM_B1 ** self.t)
         # one launch for all variables: a device table of <= 16384-element chunks, rebuilt only when a tensor moved
         ptrs = tuple(self._p(name).data_ptr() for name, _ in self.order)
+        fused = self.weight_l2 > 0                 # the l2 term and sum w^2 inside the launch; else vv_adam_step_multi's five-word records of the same chunks
         if self._adam_ptrs != ptrs:
-            recs = []
-            for name, _ in self.order:
-                p, g, m, v = self._p(name), self._g(name), self.m[name], self.v[name]
-                for off in range(0, p.numel(), ADAM_CHUNK):
-                    recs.append((p.data_ptr() + 4 * off, g.data_ptr() + 4 * off, m.data_ptr() + 4 * off, v.data_ptr() + 4 * off,
-                                 min(ADAM_CHUNK, p.numel() - off)))
-            self._adam_table = torch.from_numpy(np.asarray(recs, dtype=np.int64)).to(self.dev)
+            plan = adam_l2_plan(self.order, self.weight_l2, self.world)
+            quad = [(self._p(n).data_ptr(), self._g(n).data_ptr(), self.m[n].data_ptr(), self.v[n].data_ptr()) for n, _ in self.order]
+            table = adam_l2_table(plan, quad)
+            self._adam_table = torch.from_numpy(np.ascontiguousarray(table if fused else table[:, :5])).to(self.dev)
+            self._sumsq = torch.empty(plan.shape[0], dtype=torch.float32, device=self.dev) if fused else None
             self._adam_ptrs = ptrs
-        L.call('vv_adam_step_multi', L.ptr(self._adam_table), self._adam_table.shape[0], lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, st)
+        entry, extra = ('vv_adam_step_multi_l2', (L.ptr(self._sumsq),)) if fused else ('vv_adam_step_multi', ())
+        L.call(entry, L.ptr(self._adam_table), self._adam_table.shape[0], lr_t, ADAM_B1, ADAM_B2, ADAM_EPS, *extra, st)
         for e in (self.enc, self.dec):
             if e is not None:
                 e.weights_changed()

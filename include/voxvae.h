@@ -656,6 +656,21 @@ int vv_adam_step(float *param, const float *grad, float *m, float *v, long n, fl
 int vv_adam_step_multi(const void *chunk_table, int nchunks, float lr_t, float beta1, float beta2, float epsilon,
                        void *stream);
 
+/* vv_adam_step_multi with an l2 regulariser (loss term coef/2 * sum w^2 per chunk) folded into the gradient, and the
+ * regulariser's sum w^2 left behind by the same pass (AE3D.py:82-87).  chunk_table is a device array of nchunks records
+ * { float *param; const float *grad; float *m; float *v; long n; float coef; float pad; } (48 bytes, pointers already
+ * offset, n <= 16384).  Per element g_eff = fma(coef, w, grad), then the Adam rule on g_eff; a chunk with coef == 0
+ * gives vv_adam_step_multi's bits.  sumsq_partial [nchunks] float32: sum w^2 of the chunk's weights BEFORE the update
+ * (the weights the forward pass used) where coef != 0, summed in a fixed order (no atomics: the same state gives the
+ * same bits), and 0 where coef == 0.  grad is only read. */
+int vv_adam_step_multi_l2(const void *chunk_table, int nchunks, float lr_t, float beta1, float beta2, float epsilon,
+                          float *sumsq_partial, void *hip_stream);
+/* The six scalars of one AE3D.fit step (AE3D.py:67-90) from stats [batch,4] = per-sample (bce, TP, FP, FN) and the
+ * partials of vv_adam_step_multi_l2 (nchunks may be 0), every sum in double in a fixed order:
+ * out6 = (reg = l2 * sum w^2, pred = sum bce * inv_global_batch, reg + pred, sum TP * inv_global_batch, FP, FN). */
+int vv_ae3d_step_scalars(const float *stats, int batch, const float *sumsq_partial, int nchunks, float l2,
+                         float inv_global_batch, float *out6, void *hip_stream);
+
 /* dst[i] = (dst type) src[i] between float32 and bf16 (round to nearest even): operand casts of the mixed-precision
  * training step. */
 int vv_convert(const void *src, void *dst, long n, int src_dtype, int dst_dtype, void *stream);
