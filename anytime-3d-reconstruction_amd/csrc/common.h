@@ -250,7 +250,8 @@ void vv_wgrad_phase_launch(const void *src, const void *g, float *slabs, int bat
 // local to the 128-channel tile) of local row r sits at index vv_pg_frag_index(r, c).
 struct VvPgSlabPlan { int npos, mtiles, nitems, rows_per_tile, ntn; unsigned char nsplit[8]; unsigned short first[8]; };
 size_t vv_pg_conv_slab_bytes(int batch, int cin, int cout);
-int vv_pg_conv_slabs(const void *x, const void *w, int batch, int cin, int cout, void *ws, size_t ws_bytes, hipStream_t st, VvPgSlabPlan *plan);
+int vv_pg_conv_slabs(const void *x, const void *w, int batch, int cin, int cout, void *ws, size_t ws_bytes, bool fold, hipStream_t st,
+                     VvPgSlabPlan *plan);
 // wave = (r >> 6) * 2 + (c >> 6); nt_ = (c >> 5) & 1; mt_ = (r >> 5) & 1; g = (c >> 3) & 3; lane = ((c >> 2) & 1) * 32 + (r & 31)
 __host__ __device__ inline int vv_pg_frag_index(int r, int c) {
     return ((((((r >> 6) * 2 + (c >> 6)) * 2 + ((c >> 5) & 1)) * 2 + ((r >> 5) & 1)) * 4 + ((c >> 3) & 3)) * 64) + ((c >> 2) & 1) * 32 + (r & 31);

@@ -479,14 +479,15 @@ VV_EXPORT size_t vv_conv_pos_latent_tail_workspace_bytes(int batch, int cin4, in
     return sl + (size_t)8 * (cout4 / 256) * batch * E * sizeof(float);
 }
 
-VV_EXPORT int vv_conv_pos_latent_tail_fwd(const void *x4, const void *w4_skip, const float *scale4, const float *shift4, int cin4, int cout4,
-                                          const void *w5, const float *e5_scale, const float *eps, const void *wd, const float *scale_d,
-                                          const float *shift_d, const void *w1, const float *scale_1, const float *shift_1, float *enc_out,
-                                          float *z, void *z_act, float *kl, void *h1, int batch, int E, int L, int lin, int n1, int variational,
-                                          int act, int dtype, void *workspace, size_t workspace_bytes, void *stream) {
+VV_EXPORT int vv_conv_pos_latent_tail_fwd_ex(const void *x4, const void *w4_skip, const float *scale4, const float *shift4, int cin4, int cout4,
+                                             const void *w5, const float *e5_scale, const float *eps, const void *wd, const float *scale_d,
+                                             const float *shift_d, const void *w1, const float *scale_1, const float *shift_1, float *enc_out,
+                                             float *z, void *z_act, float *kl, void *h1, int batch, int E, int L, int lin, int n1, int variational,
+                                             int act, int schedule, void *workspace, size_t workspace_bytes, void *hip_stream) {
     if (!x4 || !w4_skip || !w5 || !wd || !w1 || !z || !h1) return VV_ERR_NULL;
     if (variational && !eps) return VV_ERR_NULL;
-    if (batch <= 0 || !vv_conv_pos_latent_tail_supported(cin4, cout4, E, L, lin, n1, variational, dtype)) return VV_ERR_SHAPE;
+    if (schedule != VV_SCHED_LATENCY && schedule != VV_SCHED_THROUGHPUT) return VV_ERR_SHAPE;
+    if (batch <= 0 || !vv_conv_pos_latent_tail_supported(cin4, cout4, E, L, lin, n1, variational, VV_BF16)) return VV_ERR_SHAPE;
     if ((size_t)E * 8 * cout4 * 2 >= 0xFFFFFFF0ull) return VV_ERR_SHAPE;
     if (!vv_aligned16(x4) || !vv_aligned16(w4_skip) || !vv_aligned16(w5) || !vv_aligned16(wd) || !vv_aligned16(w1) || !vv_aligned16(h1) ||
         !vv_aligned16(z) || (enc_out && !vv_aligned16(enc_out)) || (scale4 && !vv_aligned16(scale4)) || (shift4 && !vv_aligned16(shift4)))
@@ -495,9 +496,9 @@ VV_EXPORT int vv_conv_pos_latent_tail_fwd(const void *x4, const void *w4_skip, c
     const int nh = cout4 / 256, nslice = 8 * nh;
     if (!sl) return VV_ERR_SHAPE;
     if (!workspace || !vv_aligned16(workspace) || workspace_bytes < sl + (size_t)nslice * batch * E * sizeof(float)) return VV_ERR_WORKSPACE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     VvPgSlabPlan plan;
-    int rc = vv_pg_conv_slabs(x4, w4_skip, batch, cin4, cout4, workspace, sl, st, &plan);
+    int rc = vv_pg_conv_slabs(x4, w4_skip, batch, cin4, cout4, workspace, sl, schedule == VV_SCHED_THROUGHPUT, st, &plan);
     if (rc != VV_OK) return rc;
     LtE5xArgs a;
     a.pslabs = reinterpret_cast<const float *>(workspace);
@@ -514,4 +515,14 @@ VV_EXPORT int vv_conv_pos_latent_tail_fwd(const void *x4, const void *w4_skip, c
         if (n1 % (16 * c) == 0) { nq = c; break; }
     return lt_launch_mid(a.slabs, nslice, nq, e5_scale, eps, wd, scale_d, shift_d, w1, scale_1, shift_1, enc_out, z, z_act, kl, h1, batch, E, L, lin, n1,
                          variational, act, st);
+}
+
+VV_EXPORT int vv_conv_pos_latent_tail_fwd(const void *x4, const void *w4_skip, const float *scale4, const float *shift4, int cin4, int cout4,
+                                          const void *w5, const float *e5_scale, const float *eps, const void *wd, const float *scale_d,
+                                          const float *shift_d, const void *w1, const float *scale_1, const float *shift_1, float *enc_out,
+                                          float *z, void *z_act, float *kl, void *h1, int batch, int E, int L, int lin, int n1, int variational,
+                                          int act, int dtype, void *workspace, size_t workspace_bytes, void *stream) {
+    if (dtype != VV_BF16) return !x4 || !w4_skip || !w5 || !wd || !w1 || !z || !h1 || (variational && !eps) ? VV_ERR_NULL : VV_ERR_SHAPE;
+    return vv_conv_pos_latent_tail_fwd_ex(x4, w4_skip, scale4, shift4, cin4, cout4, w5, e5_scale, eps, wd, scale_d, shift_d, w1, scale_1, shift_1, enc_out,
+                                          z, z_act, kl, h1, batch, E, L, lin, n1, variational, act, VV_SCHED_LATENCY, workspace, workspace_bytes, stream);
 }

@@ -76,7 +76,11 @@ __host__ __device__ inline PgAxis pg_axis(int o) {
 #define PG_RD(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF) : "memory")
 #define PG_WAIT4(N, F) asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(F[0]), "+v"(F[1]), "+v"(F[2]), "+v"(F[3]) : "n"(N) : "memory")
 
-template <int MODE>
+// FOLD = false: a workgroup is one K share of the latency plan (one batch alone fills the chip).  FOLD = true: a workgroup is a whole
+// position; it walks the position's chunks in one K loop and, at every cut of the latency plan, adds the running accumulators to a
+// second set and clears them -- the float32 sums of pg_reduce_kernel, in its order, without slabs or a second launch, and the
+// per-workgroup fixed cost (ring prologue, epilogue) once per position.  For callers that keep several batches in flight.
+template <int MODE, bool FOLD>
 __global__ __launch_bounds__(512, 1) void pg_kernel(const PgArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -92,18 +96,18 @@ __global__ __launch_bounds__(512, 1) void pg_kernel(const PgArgs a) {
     const int wi = (nwg & 7) ? (int)blockIdx.x : (int)(blockIdx.x & 7) * (nwg >> 3) + (int)(blockIdx.x >> 3);
     const int mt = wi % a.mtiles;
     const int nt = (wi / a.mtiles) % a.ntn;
-    const int slot = wi / (a.mtiles * a.ntn);
+    const int slot = wi / (a.mtiles * a.ntn);             // FOLD: the position itself
     // position of this share slot: the last p with first[p] <= slot (one table entry per lane, one ballot)
     const bool le = lane < a.npos && (int)a.first[lane < PG_MAXPOS ? lane : 0] <= slot;
-    const int p = __builtin_amdgcn_readfirstlane(__builtin_popcountll(__ballot(le)) - 1);
-    const int share = slot - (int)a.first[p], nshare = a.nsplit[p];
+    const int p = FOLD ? __builtin_amdgcn_readfirstlane(slot) : __builtin_amdgcn_readfirstlane(__builtin_popcountll(__ballot(le)) - 1);
+    const int share = FOLD ? 0 : slot - (int)a.first[p], nshare = a.nsplit[p];
     // output position -> per-axis tap runs
     int od, oh, ow;
     if (MODE == 0) { od = (p >> 2) & 1; oh = (p >> 1) & 1; ow = p & 1; }
     else { od = (p >> 4) & 3; oh = (p >> 2) & 3; ow = p & 3; }
     const PgAxis xd = pg_axis<MODE>(od), xh = pg_axis<MODE>(oh), xw = pg_axis<MODE>(ow);
     const int nchunks = xd.cnt * xh.cnt * xw.cnt * NC;
-    const int c_begin = (int)((long)nchunks * share / nshare), c_end = (int)((long)nchunks * (share + 1) / nshare);
+    const int c_begin = FOLD ? 0 : (int)((long)nchunks * share / nshare), c_end = FOLD ? nchunks : (int)((long)nchunks * (share + 1) / nshare);
     const int nmine = c_end - c_begin;
     const int m0 = mt * PG_BM, n0 = nt * PG_BN;
 
@@ -154,6 +158,10 @@ __global__ __launch_bounds__(512, 1) void pg_kernel(const PgArgs a) {
             soa = (unsigned)(cell * (a.cin * 2) + c * 128);
             sow = (unsigned)((((par * 8 + ta) * NC + c) * a.cout + n0) * 128);
         }
+        if (FOLD) {       // uniform by construction; said out loud, the asm operands below are scalar registers
+            soa = __builtin_amdgcn_readfirstlane(soa);
+            sow = __builtin_amdgcn_readfirstlane(sow);
+        }
         const unsigned da = lds0 + buf * PG_STAGE + wave * 4096, db = lds0 + buf * PG_STAGE + PG_BM * 128 + wave * 2048;
 #pragma unroll
         for (int k = 0; k < 4; ++k) vv_dma16(rsx, a_lane[k], soa, da + k * 1024);
@@ -185,6 +193,19 @@ __global__ __launch_bounds__(512, 1) void pg_kernel(const PgArgs a) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    // FOLD: the shares before the running one, summed in share order from zero (pg_reduce_kernel's sum); `cut` = the chunk at which
+    // the running share of the latency plan ends (the c_end arithmetic above)
+    f32x16 total[2][2];
+    int cshare = 0, cut = 0;
+    if (FOLD) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) total[i][j][e] = 0.f;
+        cut = __builtin_amdgcn_readfirstlane(nchunks / nshare);
+    }
 
     // fragment set = {row tile 0, row tile 1, channel tile 0, channel tile 1} of one k-step (rows 32 apart: 4096 B)
     auto rd = [&](pg_u4 *F, int ks, unsigned stoff) {
@@ -231,6 +252,24 @@ __global__ __launch_bounds__(512, 1) void pg_kernel(const PgArgs a) {
         buf = buf == PG_NST - 1 ? 0 : buf + 1;
         if (i + 1 < nmine) rd(P, 0, (unsigned)buf * PG_STAGE);
         mma(Q);
+        if (FOLD && i + 1 == cut && i + 1 < nmine) {        // a share of the latency plan ends here, another follows
+#pragma unroll
+            for (int nt_ = 0; nt_ < 2; ++nt_)
+#pragma unroll
+                for (int mt_ = 0; mt_ < 2; ++mt_) {
+                    total[nt_][mt_] += acc[nt_][mt_];
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) acc[nt_][mt_][e] = 0.f;
+                }
+            ++cshare;
+            cut = __builtin_amdgcn_readfirstlane((int)((long)nchunks * (cshare + 1) / nshare));
+        }
+    }
+    if (FOLD && nshare > 1) {                              // + the last share; a one-share position keeps its accumulators as they are
+#pragma unroll
+        for (int nt_ = 0; nt_ < 2; ++nt_)
+#pragma unroll
+            for (int mt_ = 0; mt_ < 2; ++mt_) acc[nt_][mt_] = total[nt_][mt_] + acc[nt_][mt_];
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
@@ -253,7 +292,7 @@ __global__ __launch_bounds__(512, 1) void pg_kernel(const PgArgs a) {
                         f32x4{acc[nt_][mt_][4 * g], acc[nt_][mt_][4 * g + 1], acc[nt_][mt_][4 * g + 2], acc[nt_][mt_][4 * g + 3]};
         return;
     }
-    const bool final_out = nshare == 1;
+    const bool final_out = FOLD || nshare == 1;
     const int m_rows = a.batch - m0 < PG_BM ? a.batch - m0 : PG_BM;
     auto fill = [&](auto act_c, auto fin_c) {
         constexpr int ACT = decltype(act_c)::value;
@@ -397,8 +436,9 @@ size_t pg_ws_bytes(int batch, int cin, int cout) {
 
 template <int MODE>
 int pg_run(const void *x, const void *w, const float *scale, const float *shift, void *y, int batch, int cin, int cout, int act, void *ws,
-           size_t ws_bytes, hipStream_t st) {
-    vv_allow_lds<&pg_kernel<MODE>>(PG_LDS);
+           size_t ws_bytes, bool fold, hipStream_t st) {
+    vv_allow_lds<&pg_kernel<MODE, false>>(PG_LDS);
+    vv_allow_lds<&pg_kernel<MODE, true>>(PG_LDS);
     constexpr int VIN = MODE == 0 ? 64 : 8, VOUT = MODE == 0 ? 8 : 64;
     const size_t sample_in = (size_t)VIN * cin * 2, sample_out = (size_t)VOUT * cout * 2;
     int per = (int)((0x7FFFFFFFull / sample_in) / PG_BM) * PG_BM;        // 32-bit buffer offsets: <= 2 GiB of input per launch
@@ -407,7 +447,7 @@ int pg_run(const void *x, const void *w, const float *scale, const float *shift,
         const int nb = batch - s0 < per ? batch - s0 : per;
         PgArgs a;
         pg_plan<MODE>(a, nb, cin, cout);
-        const size_t need = (size_t)a.nitems * a.mtiles * PG_BM * cout * sizeof(float);
+        const size_t need = (size_t)a.nitems * a.mtiles * PG_BM * cout * sizeof(float);       // either form accepts what the query returns
         if (!ws || ws_bytes < need || !vv_aligned16(ws)) return VV_ERR_WORKSPACE;
         a.x = reinterpret_cast<const char *>(x) + (size_t)s0 * sample_in;
         a.y = reinterpret_cast<char *>(y) + (size_t)s0 * sample_out;
@@ -417,7 +457,13 @@ int pg_run(const void *x, const void *w, const float *scale, const float *shift,
         a.force_slabs = 0;
         a.x_bytes = (unsigned)((size_t)nb * sample_in);
         a.w_bytes = (unsigned)((size_t)64 * cin * cout * 2);
-        VV_LAUNCH(pg_kernel<MODE>, dim3(a.nitems * a.ntn * a.mtiles), dim3(512), PG_LDS, st, a);
+        if (fold) {                             // a workgroup per (position, channel tile, sample tile): no slabs, no reduce launch
+            VV_LAUNCH((pg_kernel<MODE, true>), dim3(a.npos * a.ntn * a.mtiles), dim3(512), PG_LDS, st, a);
+            const int rc = vv_launch_status();
+            if (rc != VV_OK) return rc;
+            continue;
+        }
+        VV_LAUNCH((pg_kernel<MODE, false>), dim3(a.nitems * a.ntn * a.mtiles), dim3(512), PG_LDS, st, a);
         int rc = vv_launch_status();
         if (rc != VV_OK) return rc;
         bool any = false;
@@ -441,7 +487,9 @@ bool pg_shape_ok(int cin, int cout) {
 
 // ---- internal (common.h): the 4^3 -> 2^3 convolution as float32 slabs ONLY -- no reduce launch, no folded BN: the consumer
 // (latent_tail.hip: lt_e5x_kernel) sums the shares of a position in share order, exactly as pg_reduce_kernel does, while it builds
-// its own MFMA operand.  One launch; the whole batch must fit 32-bit buffer offsets.
+// its own MFMA operand.  One launch; the whole batch must fit 32-bit buffer offsets.  fold: one workgroup and one slab per position,
+// the shares already summed in that order; the plan handed back then says one share per position, and the consumer's 0 + slab is the
+// same float.  The byte count is the split form's (the larger) for either.
 size_t vv_pg_conv_slab_bytes(int batch, int cin, int cout) {
     if (batch <= 0 || !pg_shape_ok(cin, cout) || (size_t)batch * 64 * cin * 2 > 0x7FFFFFFFull) return 0;
     PgArgs a;
@@ -449,8 +497,10 @@ size_t vv_pg_conv_slab_bytes(int batch, int cin, int cout) {
     return (size_t)a.nitems * a.mtiles * a.ntn * PG_BM * PG_BN * sizeof(float);      // whole [256][128] pieces in fragment order
 }
 
-int vv_pg_conv_slabs(const void *x, const void *w, int batch, int cin, int cout, void *ws, size_t ws_bytes, hipStream_t st, VvPgSlabPlan *plan) {
-    vv_allow_lds<&pg_kernel<0>>(PG_LDS);
+int vv_pg_conv_slabs(const void *x, const void *w, int batch, int cin, int cout, void *ws, size_t ws_bytes, bool fold, hipStream_t st,
+                     VvPgSlabPlan *plan) {
+    vv_allow_lds<&pg_kernel<0, false>>(PG_LDS);
+    vv_allow_lds<&pg_kernel<0, true>>(PG_LDS);
     const size_t need = vv_pg_conv_slab_bytes(batch, cin, cout);
     if (!need) return VV_ERR_SHAPE;
     if (!ws || ws_bytes < need || !vv_aligned16(ws)) return VV_ERR_WORKSPACE;
@@ -462,9 +512,16 @@ int vv_pg_conv_slabs(const void *x, const void *w, int batch, int cin, int cout,
     a.force_slabs = 1;
     a.x_bytes = (unsigned)((size_t)batch * 64 * cin * 2);
     a.w_bytes = (unsigned)((size_t)64 * cin * cout * 2);
-    VV_LAUNCH(pg_kernel<0>, dim3(a.nitems * a.ntn * a.mtiles), dim3(512), PG_LDS, st, a);
-    plan->npos = a.npos; plan->mtiles = a.mtiles; plan->nitems = a.nitems; plan->rows_per_tile = PG_BM; plan->ntn = a.ntn;
-    for (int p = 0; p < 8; ++p) { plan->nsplit[p] = a.nsplit[p]; plan->first[p] = a.first[p]; }
+    plan->npos = a.npos; plan->mtiles = a.mtiles; plan->rows_per_tile = PG_BM; plan->ntn = a.ntn;
+    if (fold) {
+        VV_LAUNCH((pg_kernel<0, true>), dim3(a.npos * a.ntn * a.mtiles), dim3(512), PG_LDS, st, a);
+        plan->nitems = a.npos;
+        for (int p = 0; p < 8; ++p) { plan->nsplit[p] = 1; plan->first[p] = (unsigned short)p; }
+    } else {
+        VV_LAUNCH((pg_kernel<0, false>), dim3(a.nitems * a.ntn * a.mtiles), dim3(512), PG_LDS, st, a);
+        plan->nitems = a.nitems;
+        for (int p = 0; p < 8; ++p) { plan->nsplit[p] = a.nsplit[p]; plan->first[p] = a.first[p]; }
+    }
     return vv_launch_status();
 }
 
@@ -486,20 +543,38 @@ VV_EXPORT size_t vv_convT3d_k4s2_pos_workspace_bytes(int batch, int cin, int cou
     return pg_ws_bytes<1>(batch < (1 << 20) ? batch : (1 << 20), cin, cout);
 }
 
-VV_EXPORT int vv_conv3d_k4s2_pos_fwd(const void *x, const void *w_skip, const float *scale, const float *shift, void *y, int batch,
-                                     int side, int cin, int cout, int act, int dtype, void *workspace, size_t workspace_bytes, void *stream) {
+VV_EXPORT int vv_conv3d_k4s2_pos_fwd_ex(const void *x, const void *w_skip, const float *scale, const float *shift, void *y, int batch,
+                                        int side, int cin, int cout, int act, int schedule, void *workspace, size_t workspace_bytes,
+                                        void *hip_stream) {
     if (!x || !w_skip || !y) return VV_ERR_NULL;
-    if (!vv_conv3d_k4s2_pos_supported(side, cin, cout, dtype) || batch <= 0) return VV_ERR_SHAPE;
+    if (schedule != VV_SCHED_LATENCY && schedule != VV_SCHED_THROUGHPUT) return VV_ERR_SHAPE;
+    if (!vv_conv3d_k4s2_pos_supported(side, cin, cout, VV_BF16) || batch <= 0) return VV_ERR_SHAPE;
     if (!vv_aligned16(x) || !vv_aligned16(w_skip) || !vv_aligned16(y) || (scale && !vv_aligned16(scale)) || (shift && !vv_aligned16(shift)))
         return VV_ERR_ALIGN;
-    return pg_run<0>(x, w_skip, scale, shift, y, batch, cin, cout, act, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+    return pg_run<0>(x, w_skip, scale, shift, y, batch, cin, cout, act, workspace, workspace_bytes, schedule == VV_SCHED_THROUGHPUT,
+                     reinterpret_cast<hipStream_t>(hip_stream));
+}
+
+VV_EXPORT int vv_conv3d_k4s2_pos_fwd(const void *x, const void *w_skip, const float *scale, const float *shift, void *y, int batch,
+                                     int side, int cin, int cout, int act, int dtype, void *workspace, size_t workspace_bytes, void *stream) {
+    if (dtype != VV_BF16) return !x || !w_skip || !y ? VV_ERR_NULL : VV_ERR_SHAPE;
+    return vv_conv3d_k4s2_pos_fwd_ex(x, w_skip, scale, shift, y, batch, side, cin, cout, act, VV_SCHED_LATENCY, workspace, workspace_bytes, stream);
+}
+
+VV_EXPORT int vv_convT3d_k4s2_pos_fwd_ex(const void *x, const void *w_skip, const float *scale, const float *shift, void *y, int batch,
+                                         int side, int cin, int cout, int act, int schedule, void *workspace, size_t workspace_bytes,
+                                         void *hip_stream) {
+    if (!x || !w_skip || !y) return VV_ERR_NULL;
+    if (schedule != VV_SCHED_LATENCY && schedule != VV_SCHED_THROUGHPUT) return VV_ERR_SHAPE;
+    if (!vv_convT3d_k4s2_pos_supported(side, cin, cout, VV_BF16) || batch <= 0) return VV_ERR_SHAPE;
+    if (!vv_aligned16(x) || !vv_aligned16(w_skip) || !vv_aligned16(y) || (scale && !vv_aligned16(scale)) || (shift && !vv_aligned16(shift)))
+        return VV_ERR_ALIGN;
+    return pg_run<1>(x, w_skip, scale, shift, y, batch, cin, cout, act, workspace, workspace_bytes, schedule == VV_SCHED_THROUGHPUT,
+                     reinterpret_cast<hipStream_t>(hip_stream));
 }
 
 VV_EXPORT int vv_convT3d_k4s2_pos_fwd(const void *x, const void *w_skip, const float *scale, const float *shift, void *y, int batch,
                                       int side, int cin, int cout, int act, int dtype, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!x || !w_skip || !y) return VV_ERR_NULL;
-    if (!vv_convT3d_k4s2_pos_supported(side, cin, cout, dtype) || batch <= 0) return VV_ERR_SHAPE;
-    if (!vv_aligned16(x) || !vv_aligned16(w_skip) || !vv_aligned16(y) || (scale && !vv_aligned16(scale)) || (shift && !vv_aligned16(shift)))
-        return VV_ERR_ALIGN;
-    return pg_run<1>(x, w_skip, scale, shift, y, batch, cin, cout, act, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+    if (dtype != VV_BF16) return !x || !w_skip || !y ? VV_ERR_NULL : VV_ERR_SHAPE;
+    return vv_convT3d_k4s2_pos_fwd_ex(x, w_skip, scale, shift, y, batch, side, cin, cout, act, VV_SCHED_LATENCY, workspace, workspace_bytes, stream);
 }

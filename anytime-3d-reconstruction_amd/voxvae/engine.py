@@ -6,6 +6,7 @@ tensors), the packed MFMA panels derived from them and the layer chain, and driv
 arithmetic step is a libvoxvae kernel.  Reference: src/net_core/autoencoder3D.py:72-139.
 """
 import collections
+import contextlib
 import ctypes
 import functools
 
@@ -161,6 +162,9 @@ class _EngineBase:
         self.act = L.ACT[structure['activation']]
         self.timer = None         # LayerTimer or None
         self.tag = ''
+        # vv_schedule of the 4^3 <-> 2^3 layers: latency for a caller that runs one batch at a time; the evaluators that keep several
+        # batches in flight on their own streams (voxvae/streams.py) switch to throughput around each submit (`scheduled`)
+        self.schedule = L.VV_SCHED_LATENCY
 
     def _call(self, layer, fn, *args):
         t = self.timer
@@ -362,7 +366,7 @@ class EncoderEngine(_EngineBase):
                 return h
             o = self._empty(B, side // 2, side // 2, side // 2, f[i], dtype=torch.uint8 if ly.odt == L.VV_FP8 else None)
             R.launch_conv(functools.partial(self._call, ly.name), ly.route, self.ws, h, ly.w, pk['scale%d' % i], pk['shift%d' % i], o,
-                          B, side, f[i - 1], f[i], self.act, self.dt, ly.odt, st)
+                          B, side, f[i - 1], f[i], self.act, self.dt, ly.odt, st, schedule=self.schedule)
             h, side, hdt = o, side // 2, ly.odt
         i = len(f) - 1
         K = side ** 3 * f[i - 1]
@@ -497,7 +501,7 @@ class DecoderEngine(_EngineBase):
                 odt = L.VV_FP8
             o = self._empty(B, 2 * side, 2 * side, 2 * side, f[i], dtype=torch.uint8 if odt == L.VV_FP8 else None)
             R.launch_convT(functools.partial(self._call, ly.name), ly.route, self.ws, h, ly.w, pk['scale%d' % i], pk['shift%d' % i], o,
-                           B, side, f[i - 1], f[i], self.act, self.dt, odt, st)
+                           B, side, f[i - 1], f[i], self.act, self.dt, odt, st, schedule=self.schedule)
             h, side, hdt = o, 2 * side, odt
         return h, hdt, side, B
 
@@ -588,6 +592,20 @@ def reparam_kl(enc_out, eps, latent, act_dtype, drop_mask=None, drop_scale=1.0, 
     return z, z_act, kl, mean, logvar
 
 
+@contextlib.contextmanager
+def scheduled(engines, schedule):
+    """The engines issue their 4^3 <-> 2^3 layers with `schedule` (vv_schedule) inside the block.  The results are the same bits; what
+    changes is how many workgroups a launch takes (include/voxvae.h)."""
+    old = [e.schedule for e in engines]
+    for e in engines:
+        e.schedule = schedule
+    try:
+        yield
+    finally:
+        for e, s in zip(engines, old):
+            e.schedule = s
+
+
 def latent_tail_supported(enc, dec, variational):
     """True when encoder tail -> reparam/KL -> Dense -> first decoder layer can run as the two fused launches of latent_tail.hip."""
     if getattr(enc, 'pool_max', False) or getattr(enc, 'pool_none', False) or getattr(enc, 'final_sigmoid', False):
@@ -636,8 +654,11 @@ def latent_tail(enc, dec, h, eps, variational, want_enc_out=False, pos_layer=Fal
     if pos_layer:
         c3, c4, i4 = enc.filters[-3], enc.filters[-2], ne - 1
         ws = enc.ws.get(L.load().vv_conv_pos_latent_tail_workspace_bytes(B, c3, c4, E))
-        enc._call('E%dLT' % ne, 'vv_conv_pos_latent_tail_fwd', L.ptr(h), L.ptr(enc.plan[-1].w), L.ptr(pe['scale%d' % i4]), L.ptr(pe['shift%d' % i4]),
-                  c3, c4, *tail, E, Lz, lin, n1, int(variational), dec.act, L.VV_BF16, L.ptr(ws), ws.numel(), _stream())
+        head = (L.ptr(h), L.ptr(enc.plan[-1].w), L.ptr(pe['scale%d' % i4]), L.ptr(pe['shift%d' % i4]), c3, c4, *tail, E, Lz, lin, n1, int(variational), dec.act)
+        if enc.schedule == L.VV_SCHED_LATENCY:
+            enc._call('E%dLT' % ne, 'vv_conv_pos_latent_tail_fwd', *head, L.VV_BF16, L.ptr(ws), ws.numel(), _stream())
+        else:
+            enc._call('E%dLT' % ne, 'vv_conv_pos_latent_tail_fwd_ex', *head, enc.schedule, L.ptr(ws), ws.numel(), _stream())
     else:
         ws = enc.ws.get(L.load().vv_latent_tail_workspace_bytes(B, K5, E, n1))
         enc._call('LT', 'vv_latent_tail_fwd', L.ptr(h), *tail, K5, E, Lz, lin, n1, int(variational), dec.act, L.VV_BF16, L.ptr(ws), ws.numel(),

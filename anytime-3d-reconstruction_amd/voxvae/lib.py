@@ -21,6 +21,7 @@ HOOK_VARS = ('VV_CD_SHAPE', 'VV_CDH_STAGGER', 'VV_CDH_ABL', 'VV_DIRECT_MT', 'VV_
              'VV_NO_WGRAD_PHASE', 'VV_BN_NB', 'VV_BN_SWEEP', 'VV_FINAL_BCE', 'VV_FIRSTCONV_GATHER', 'VV_FIRSTCONV_WGS', 'VV_FIRSTCONV_NOCHAIN', 'VV_CHUNK_SAMPLES', 'VV_C2_SPLITS')
 
 VV_F32, VV_BF16, VV_FP8 = 0, 1, 2
+VV_SCHED_LATENCY, VV_SCHED_THROUGHPUT = 0, 1        # vv_schedule: how the *_ex entries of the 4^3 <-> 2^3 layers cut their work (same bits either way)
 ACT = {None: 0, 'None': 0, 'linear': 0, 'elu': 1, 'relu': 2, 'lrelu': 3}
 DTYPES = {'f32': VV_F32, 'fp32': VV_F32, 'float32': VV_F32, 'bf16': VV_BF16, 'bfloat16': VV_BF16, 'fp8': VV_FP8}
 
@@ -74,6 +75,8 @@ SIGNATURES = {
     'vv_convT3d_k4s2_pos_workspace_bytes': (_sz, [_i, _i, _i]),
     'vv_conv3d_k4s2_pos_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'vv_convT3d_k4s2_pos_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'vv_conv3d_k4s2_pos_fwd_ex': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'vv_convT3d_k4s2_pos_fwd_ex': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'vv_dense_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'vv_dense_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'vv_latent_tail_supported': (_i, [_i, _i, _i, _i, _i, _i, _i]),
@@ -82,6 +85,7 @@ SIGNATURES = {
     'vv_conv_pos_latent_tail_supported': (_i, [_i] * 8),
     'vv_conv_pos_latent_tail_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'vv_conv_pos_latent_tail_fwd': (_i, [_vp] * 4 + [_i, _i] + [_vp] * 14 + [_i] * 8 + [_vp, _sz, _vp]),
+    'vv_conv_pos_latent_tail_fwd_ex': (_i, [_vp] * 4 + [_i, _i] + [_vp] * 14 + [_i] * 8 + [_vp, _sz, _vp]),
     'vv_reparam_kl_fwd': (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp]),
     'vv_convT3d_final_bce_workspace_bytes': (_sz, [_i, _i]),
     'vv_convT3d_final_bce_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _sz, _vp]),

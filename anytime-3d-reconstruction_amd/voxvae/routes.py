@@ -168,11 +168,15 @@ def pack_image(direction, kind, w_keras, cin, cout, dt, st):
 # ---- launches.  call(fn, *args) issues one library call (the engines wrap it in their layer timer); wsp is a _Workspace.
 # odt: element type of y for the engines' entry points; None = the training step's entry points (raw output in dt, which the
 # trainer calls with scale = shift = None and act = 0: BatchNorm follows with batch statistics).
-def _launch(fn, call, route, wsp, x, w, scale, shift, y, B, side, cin, cout, act, dt, odt, st):
+# schedule: vv_schedule of the 'pos' form (the other forms have only one); the workspace query serves either.
+def _launch(fn, call, route, wsp, x, w, scale, shift, y, B, side, cin, cout, act, dt, odt, st, schedule=L.VV_SCHED_LATENCY):
     head = (L.ptr(x), L.ptr(w), L.ptr(scale), L.ptr(shift), L.ptr(y), B, side, cin, cout, act)
     if route == 'pos':
         ws = wsp.get(getattr(L.load(), fn + '_pos_workspace_bytes')(B, cin, cout))
-        call(fn + '_pos_fwd', *head, dt, L.ptr(ws), ws.numel(), st)
+        if schedule == L.VV_SCHED_LATENCY:
+            call(fn + '_pos_fwd', *head, dt, L.ptr(ws), ws.numel(), st)
+        else:
+            call(fn + '_pos_fwd_ex', *head, schedule, L.ptr(ws), ws.numel(), st)
     elif route == 'direct_fp8':
         call(fn + '_direct_fp8_fwd', *head, odt, st)
     elif route == 'direct' and odt is not None and fn == 'vv_conv3d_k4s2':

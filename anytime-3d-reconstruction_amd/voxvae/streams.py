@@ -16,6 +16,9 @@ Measured on MI355X (32^3, batch 256, bf16; profiles/microbench/mb_streams3.py, f
 """
 import torch
 
+from . import engine as _E
+from . import lib as _L
+
 
 def _engines(model):
     """The engines of a model (the image -> 3D model has no voxel encoder)."""
@@ -73,7 +76,9 @@ class StreamedEvaluator:
         for t in (x, y, eps):
             if torch.is_tensor(t) and t.is_cuda:
                 t.record_stream(s)                 # the caller may free its inputs before this stream has read them
-        with torch.cuda.stream(s):
+        # several batches in flight: the 4^3 <-> 2^3 layers take one workgroup per output position instead of one per K share
+        # (same bits; a launch then costs the device less while the other streams' workgroups fill it)
+        with torch.cuda.stream(s), _E.scheduled(_engines(self.models[i]), _L.VV_SCHED_THROUGHPUT):
             out = self.models[i].eval_forward_device(x, y, eps)
         self.last_stream = s
         return out
@@ -141,7 +146,7 @@ class HostPipeline:
         s.wait_stream(cur)
         m._lazy_host = True
         try:
-            with torch.cuda.stream(s):
+            with torch.cuda.stream(s), _E.scheduled(engines, _L.VV_SCHED_THROUGHPUT if self.depth > 1 else _L.VV_SCHED_LATENCY):
                 out = m.getEval(inputs=inputs, category_vectors=category_vectors, missing_prob=missing_prob, **kw)
                 ev = torch.cuda.Event()
                 ev.record(s)

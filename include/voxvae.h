@@ -31,6 +31,11 @@ extern "C" {
 
 typedef enum { VV_F32 = 0, VV_BF16 = 1, VV_FP8 = 2 /* OCP e4m3fn, 1 byte; MFMA layers with cin % 128 == 0 only */ } vv_dtype;
 typedef enum { VV_ACT_NONE = 0, VV_ACT_ELU = 1, VV_ACT_RELU = 2, VV_ACT_LRELU = 3 } vv_act;
+/* How an entry with a `schedule` argument cuts its work (the *_ex entries of the 4^3 <-> 2^3 layers).  The results are the same bits
+ * either way.  VV_SCHED_LATENCY: for one batch at a time -- every launch is cut fine enough to fill the device on its own.
+ * VV_SCHED_THROUGHPUT: for a caller that keeps several independent batches in flight on different streams -- fewer, longer
+ * workgroups, so that a launch costs the device less in total while another batch's workgroups fill the rest of it. */
+typedef enum { VV_SCHED_LATENCY = 0, VV_SCHED_THROUGHPUT = 1 } vv_schedule;
 typedef enum {
     VV_OK = 0,
     VV_ERR_NULL = -1,       /* required pointer is NULL */
@@ -194,6 +199,17 @@ int vv_conv3d_k4s2_pos_fwd(const void *x, const void *w_skip, const float *scale
                            int side, int cin, int cout, int act, int dtype, void *workspace, size_t workspace_bytes, void *stream);
 int vv_convT3d_k4s2_pos_fwd(const void *x, const void *w_skip, const float *scale, const float *shift, void *y, int batch,
                             int side, int cin, int cout, int act, int dtype, void *workspace, size_t workspace_bytes, void *stream);
+/* The same with a `schedule` (vv_schedule; anything else: VV_ERR_SHAPE); the entries above are VV_SCHED_LATENCY.  bf16 is the only
+ * element type of this form, so these take none.  VV_SCHED_THROUGHPUT: one workgroup walks ALL K shares of its output position and
+ * adds them up in registers, in the share order and with the float32 sums of the split form -- every output byte is the same; no
+ * slabs are written and no second launch sums them.  The workspace query and check are those of the split form for either schedule
+ * (the folded form does not touch the workspace). */
+int vv_conv3d_k4s2_pos_fwd_ex(const void *x, const void *w_skip, const float *scale, const float *shift, void *y, int batch,
+                              int side, int cin, int cout, int act, int schedule, void *workspace, size_t workspace_bytes,
+                              void *hip_stream);
+int vv_convT3d_k4s2_pos_fwd_ex(const void *x, const void *w_skip, const float *scale, const float *shift, void *y, int batch,
+                               int side, int cin, int cout, int act, int schedule, void *workspace, size_t workspace_bytes,
+                               void *hip_stream);
 
 /* y[M,N] = act((x[M,K] @ w_packed[N,K]^T) * scale[N] + shift[N]): linearTransform (autoencoder3D.py:56-70) and
  * the two layers packed as dense panels above.  K % 8 == 0 (bf16) / % 4 (f32), N % 4 == 0 (tails are masked).
@@ -228,6 +244,14 @@ int vv_conv_pos_latent_tail_fwd(const void *x4, const void *w4_skip, const float
                                 const float *shift_d, const void *w1, const float *scale_1, const float *shift_1, float *enc_out,
                                 float *z, void *z_act, float *kl, void *h1, int batch, int E, int L, int lin, int n1, int variational,
                                 int act, int dtype, void *workspace, size_t workspace_bytes, void *stream);
+/* The same with a `schedule` (vv_schedule, as vv_conv3d_k4s2_pos_fwd_ex: bf16 only, no element type; the entry above is
+ * VV_SCHED_LATENCY).  VV_SCHED_THROUGHPUT: the convolution leaves ONE float32 slab per output position, its shares already summed in
+ * share order; every output byte is the same.  The workspace query serves either schedule. */
+int vv_conv_pos_latent_tail_fwd_ex(const void *x4, const void *w4_skip, const float *scale4, const float *shift4, int cin4, int cout4,
+                                   const void *w5, const float *e5_scale, const float *eps, const void *wd, const float *scale_d,
+                                   const float *shift_d, const void *w1, const float *scale_1, const float *shift_1, float *enc_out,
+                                   float *z, void *z_act, float *kl, void *h1, int batch, int E, int L, int lin, int n1, int variational,
+                                   int act, int schedule, void *workspace, size_t workspace_bytes, void *hip_stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Latent ops */
