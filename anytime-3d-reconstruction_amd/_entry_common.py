@@ -53,9 +53,20 @@ def parse(description, train=False, extra=None):
     ap.add_argument('--dump-dir', default=None, help='test_modelnet_VAE.py: save <missing_pr>_cl_label/_gt/_pred.npy here (reference :159-165)')
     ap.add_argument('--points-dir', default=None, help='test_modelnet_VAE.py: save every batch\'s predictions as point clouds here (batch_<n>_points.npy [N,3], batch_<n>_offsets.npy [B+1]; voxvae.points); needs --pipeline 1')
     ap.add_argument('--sampling', type=int, default=0, help='test_modelnet_VAE.py: also score the sampled-mean reconstruction over this many latents per object (0 = off); needs --pipeline 1.  test_modelnet_PR.py: also accumulate that reconstruction\'s curve')
+    ap.add_argument('--mask-source', default=None, choices=['host', 'device'],
+                    help="where uninjected dropout / missing-latent masks are drawn: 'host' (np.random, the reference's calls) or 'device' "
+                         "(voxvae.masks, no upload); default: VOXVAE_MASK_SOURCE, else 'host'")
+    ap.add_argument('--seed', type=int, default=None, help='seed of the device mask source (voxvae.manual_seed) and of np.random')
     if extra is not None:
         extra(ap)
     a = ap.parse_args()
+    # both are read when a model is built, which every script does after parse(): passed on from here, once for all of them
+    import voxvae
+    if a.mask_source is not None:
+        voxvae.set_mask_source(a.mask_source)
+    if a.seed is not None:
+        voxvae.manual_seed(a.seed)
+        np.random.seed(a.seed % 2 ** 32)
     if a.points_dir and extra is None:
         if os.path.basename(sys.argv[0]) != SAMPLING_SCRIPT:
             ap.error('--points-dir is an option of %s' % SAMPLING_SCRIPT)

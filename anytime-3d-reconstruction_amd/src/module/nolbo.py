@@ -12,7 +12,9 @@ The reference draws three random tensors inside these methods (the sampling epsi
 np.random mask, :1475; the prior epsilon, :1508) and the dropout rate/mask (:1423-1425).  They are drawn here
 the same way by default (mask through np.random.choice with the same arguments, so seeding np.random
 reproduces the reference's mask stream); the keyword-only `_eps`, `_mask`, `_eps2` arguments (an extension)
-inject them, which is what makes bit-level parity tests possible.
+inject them, which is what makes bit-level parity tests possible.  With voxvae.set_mask_source('device') the uninjected keep
+masks (dropout, missing latents) are drawn on the device instead, by the model's voxvae.masks.KeepMasks: no upload, and a
+host twin that reproduces any step's mask; the default is the host draw.
 """
 import ctypes
 import os
@@ -34,6 +36,7 @@ def _st():
 
 class _ModelnetBase(object):
     _variational = True
+    _keep_masks = None      # voxvae.mask_source() == 'device' when the model was built: its voxvae.masks.KeepMasks stream
 
     @property
     def _latent_dim(self):
@@ -47,7 +50,19 @@ class _ModelnetBase(object):
         self._enc_eng, self._dec_eng = self._encoder._engine, self._decoder._engine
         self._device = self._enc_eng.device
         self._act_dt = self._dec_eng.dt
+        self._init_masks()
         print('done')
+
+    def _init_masks(self):
+        """Where the uninjected keep masks come from, read as the model is built (voxvae.set_mask_source): None = np.random on the
+        host, the reference's calls; 'device' = a KeepMasks stream of this model's own (no upload, voxvae/masks.py)."""
+        import voxvae
+        from voxvae import masks as _M
+        self._keep_masks = _M.KeepMasks(self._device) if voxvae.mask_source() == 'device' else None
+
+    def _draw_keep(self, B, Lz, rate):
+        """The device source's dropout mask [B, L] for this step, or None where the host draws it."""
+        return None if self._keep_masks is None else self._keep_masks.dropout(B, Lz, rate)
 
     # ---------------------------------------------------------------- device-side building blocks
     def _dev(self, a):
@@ -63,10 +78,13 @@ class _ModelnetBase(object):
         """A sampling / prior epsilon [B,L]: torch.randn for the reference's tf.random.normal (nolbo.py:1470, 1508) unless injected."""
         return torch.randn(B, self._latent_dim, dtype=torch.float32, device=self._device) if eps is None else self._dev(eps)
 
-    def _draw_mask(self, B, missing_prob, mask=None):
-        """The missing-latent mask [B,L] (1 = kept): reference nolbo.py:1475-1476, same RNG call, unless injected."""
+    def _draw_mask(self, B, missing_prob, mask=None, Lz=None):
+        """The missing-latent mask [B,L] (1 = kept): reference nolbo.py:1475-1476, same RNG call, unless injected or the model draws
+        its masks on the device."""
         if mask is None:
-            Lz = self._latent_dim
+            Lz = self._latent_dim if Lz is None else Lz
+            if self._keep_masks is not None:
+                return self._keep_masks.missing(B, Lz, missing_prob)
             mask = np.reshape(np.random.choice(2, B * Lz, p=[missing_prob, 1. - missing_prob]), [B, Lz]).astype('float32')
         return self._dev(mask)
 
@@ -167,6 +185,8 @@ class _ModelnetBase(object):
         mask, scale = None, 1.0
         if self._dropout:      # reference nolbo.py:1423-1425: rate ~ U[0,1) per step, inverted dropout on z
             rate = float(np.random.rand()) if drop_rate is None else float(drop_rate)
+            if drop_mask is None:
+                drop_mask = self._draw_keep(x.shape[0], self._latent_dim, rate)
             if drop_mask is None:
                 drop_mask = (np.random.rand(x.shape[0], self._latent_dim) >= rate).astype('float32')
             mask, scale = self._dev(drop_mask), 1.0 / (1.0 - rate)
@@ -550,6 +570,7 @@ class nolboSingleObject_VAE(_ModelnetBase):
                                                 last_pooling='max', activation=self._enc_head_str['activation'],
                                                 device=self._device)
         self._trainer2d = None
+        self._init_masks()
         print('done')
 
     def _encoder_2d(self, x, training=False):
@@ -598,7 +619,8 @@ class nolboSingleObject_VAE(_ModelnetBase):
         drop_mask, drop_scale = None, 1.0
         if self._dropout:
             rate, keep = _dropout if _dropout is not None else (float(np.random.rand()), None)
-            keep = (torch.rand(B, Lz, device=self._device) >= rate).float() if keep is None else self._dev(keep)
+            keep = self._draw_keep(B, Lz, rate) if keep is None else self._dev(keep)
+            keep = (torch.rand(B, Lz, device=self._device) >= rate).float() if keep is None else keep
             drop_mask, drop_scale = keep, 1.0 / (1.0 - rate)
         kl, stats, metrics, de = self._trainer2d.step_from_latent(enc_out.detach().contiguous(), y, eps, drop_mask, drop_scale,
                                                                    l2=ae3D.L2_REG)      # + decoder.losses, nolbo.py:819-823
@@ -682,7 +704,8 @@ class nolboSingleObject_modelnet_category_only(_ModelnetBase):
         drop = None
         if dropout:
             rate = float(r.get('drop_rate', np.random.rand()))
-            keep = self._dev(r['drop_keep']) if 'drop_keep' in r else (torch.rand(B, Lz, device=dev) >= rate).float()
+            keep = self._dev(r['drop_keep']) if 'drop_keep' in r else self._draw_keep(B, Lz, rate)
+            keep = (torch.rand(B, Lz, device=dev) >= rate).float() if keep is None else keep
             drop = (keep, 1.0 / (1.0 - rate))
         dist = 2.0 * Lz
 
@@ -873,9 +896,7 @@ class nolboSingleObject(nolboSingleObject_VAE):
         eps = self._draw_eps(B, _eps).contiguous()
         mask = eps2 = None
         if missing_prob > 0:
-            if _mask is None:                                                          # :202-203, the same RNG call
-                _mask = np.reshape(np.random.choice(2, B * Lc, p=[missing_prob, 1. - missing_prob]), [B, Lc]).astype('float32')
-            mask = self._dev(_mask).contiguous()
+            mask = self._draw_mask(B, missing_prob, _mask, Lc).contiguous()             # :202-203, the same RNG call
             eps2 = (torch.randn(B, Lc, dtype=torch.float32, device=self._device) if _eps2 is None else self._dev(_eps2)).contiguous()
         act_dt = _L.VV_F32 if training else self._act_dt                               # training: float32 to the decoder entry (_eval_hooks)
         new = lambda dt=torch.float32: torch.empty(B, Lc + Li, dtype=dt, device=self._device)
@@ -952,7 +973,8 @@ class nolboSingleObject_AE(nolboSingleObject_VAE):
         z_in, keep = z.detach().float().contiguous(), None
         if self._dropout:
             rate, keep = _dropout if _dropout is not None else (float(np.random.rand()), None)
-            keep = (torch.rand(z_in.shape, device=self._device) >= rate).float() if keep is None else self._dev(keep)
+            keep = self._draw_keep(z_in.shape[0], z_in.shape[1], rate) if keep is None else self._dev(keep)
+            keep = (torch.rand(z_in.shape, device=self._device) >= rate).float() if keep is None else keep
             keep = keep * (1.0 / (1.0 - rate))
             z_in = z_in * keep
         _, m, dz = self._trainer2d.step_decoder(z_in, y, l2=ae3D.L2_REG)               # + decoder.losses, :595-596

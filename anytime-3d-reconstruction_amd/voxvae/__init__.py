@@ -4,11 +4,13 @@
     engine     encoder / decoder layer chains over that ABI
     synthetic  seeded configs, weights and voxel batches (no dataset ships with the reference)
     tensor     DeviceArray, the np.array()-able handle the model API returns
+    masks      KeepMasks: dropout / missing-latent masks drawn on the device from a counter-based generator, with a host twin
 """
 import os
 
 _DEFAULTS = {'dtype': os.environ.get('VOXVAE_DTYPE', 'f32'), 'device': os.environ.get('VOXVAE_DEVICE', 'cuda:0'),
-             'fp8_policy': os.environ.get('VV_FP8_POLICY', 'mid'), 'image_engine': os.environ.get('VOXVAE_IMAGE_ENGINE', 'torch')}
+             'fp8_policy': os.environ.get('VV_FP8_POLICY', 'mid'), 'image_engine': os.environ.get('VOXVAE_IMAGE_ENGINE', 'torch'),
+             'mask_source': os.environ.get('VOXVAE_MASK_SOURCE', 'host')}
 
 
 def set_default_dtype(dtype):
@@ -54,6 +56,26 @@ def set_image_engine(engine):
 
 def image_engine():
     return _DEFAULTS['image_engine']
+
+
+def set_mask_source(source):
+    """Where models built afterwards draw their Bernoulli keep masks over [B, L] -- the dropout mask of fit and the missing-latent mask
+    of getEval(missing_prob > 0) -- when none is injected: 'host' (default: np.random, the reference's calls, uploaded) or 'device'
+    (voxvae.masks.KeepMasks: Philox4x32-10 on the device, no upload, seeded by manual_seed).  Environment: VOXVAE_MASK_SOURCE."""
+    if source not in ('host', 'device'):
+        raise ValueError(source)
+    _DEFAULTS['mask_source'] = source
+
+
+def mask_source():
+    return _DEFAULTS['mask_source']
+
+
+def manual_seed(seed):
+    """The 64-bit seed of the device mask source.  Left unset, it is taken once from np.random at the first device draw: that consumes
+    one host draw, in 'device' mode only (voxvae/masks.py)."""
+    from . import masks
+    masks.manual_seed(seed)
 
 
 def set_default_device(device):

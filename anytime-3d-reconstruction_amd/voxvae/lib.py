@@ -26,6 +26,7 @@ ACT = {None: 0, 'None': 0, 'linear': 0, 'elu': 1, 'relu': 2, 'lrelu': 3}
 DTYPES = {'f32': VV_F32, 'fp32': VV_F32, 'float32': VV_F32, 'bf16': VV_BF16, 'bfloat16': VV_BF16, 'fp8': VV_FP8}
 
 _vp, _i, _f, _sz, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
+_u64 = ctypes.c_ulonglong
 
 # name -> (restype, argtypes); mirrors include/voxvae.h one to one (tests/test_abi.py checks the header)
 SIGNATURES = {
@@ -159,6 +160,9 @@ SIGNATURES = {
     'vv_bce_bwd': (_i, [_vp, _vp, _vp, _i, _l, _f, _f, _f, _vp]),
     'vv_reparam_kl_bwd': (_i, [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _f, _vp]),
     'vv_adam_step': (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _vp]),
+    'vv_keep_mask': (_i, [_vp, _i, _i, _f, _u64, _u64, _vp]),
+    'vv_keep_mask_host': (_i, [_vp, _i, _i, _f, _u64, _u64]),
+    'vv_mask_scale': (_i, [_vp, _vp, _f, _vp, _i, _i, _vp]),
 }
 
 

@@ -659,10 +659,16 @@ class Trainer:
             z, z_act, kl, _, _ = E.reparam_kl(enc_out, eps, Lz, self.dt, drop_mask, drop_scale)
         else:
             z, kl = enc_out, None
+            if drop_mask is not None:       # inverted dropout on the encoder output (reference nolbo.py:1238-1240)
+                z = self._mask_scale(enc_out, drop_mask, drop_scale, B)
             z_act = self._cast(z)
-            if drop_mask is not None:
-                raise NotImplementedError('latent dropout for the AE class')
         return z, z_act, kl, eps
+
+    def _mask_scale(self, x, keep, scale, B):
+        """(x * keep) * scale over a float32 [B, L] latent: the forward of the autoencoder's dropout and, on dz, its backward."""
+        y = self._empty(B, self.dec.L)
+        L.call('vv_mask_scale', L.ptr(x), L.ptr(keep), float(scale), L.ptr(y), B, self.dec.L, _st())
+        return y
 
     def latent_training_mode(self, x, eps=None):
         """Encoder half of forward_training_mode -> (z float32 [B,L], z_act, kl or None).  BOTH engines are packed here (one _begin
@@ -782,7 +788,7 @@ class Trainer:
             L.call('vv_reparam_kl_bwd', L.ptr(enc_out), L.ptr(eps), L.ptr(dz), L.ptr(drop_mask), float(drop_scale), L.ptr(de), B, Lz,
                    inv_gb, st)
         else:
-            de = dz
+            de = dz if drop_mask is None else self._mask_scale(dz, drop_mask, drop_scale, B)
         if self.debug is not None:
             self.debug.update({'dlogit': dlogit, 'probs': probs, 'enc_out': enc_out, 'z': z, 'dz': dz, 'de': de, 'c_d0': c_d0, 'dcv0': dcv0,
                                't0': t0, 'dt0': dt0, 'h_dec': dh_, 'c_dec': dc_})

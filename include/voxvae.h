@@ -706,6 +706,21 @@ int vv_convert(const void *src, void *dst, long n, int src_dtype, int dst_dtype,
 int vv_unpack_bits_gather(const void *packed, const int *index, float *out, int batch, long voxels, void *stream);
 int vv_pack_bits(const float *x, void *packed, float threshold, long n, void *stream);
 
+/* ---- Bernoulli keep masks from a counter-based generator, and inverted dropout on a float32 latent (csrc/keep_mask.h: the
+ * dropout mask of fit, nolbo.py:1423-1425, and the missing-latent mask of getEval, :1475-1476; keep = u >= p in both).
+ * vv_keep_mask: keep [batch, latent] float32 (1.0f kept, 0.0f dropped), the mask format of vv_reparam_kl_fwd / _bwd.
+ *   Element e = b * latent + j is word e & 3 of the Philox4x32-10 block with counter (blk_lo, blk_hi, offset_lo, offset_hi),
+ *   blk = e >> 2, and key (seed_lo, seed_hi); u = float(word >> 8) * 2^-24 in [0, 1 - 2^-24]; keep = u >= rate.  One launch.
+ * vv_keep_mask_host: the same arithmetic in a loop on host pointers, bit for bit the device's mask; needs no GPU.
+ * vv_mask_scale: y = (x * keep) * scale in float32 (two roundings), x, keep, y [batch, latent]; x and y are distinct
+ *   buffers.  The forward of autoencoder dropout on the encoder output and its backward on dz.  One launch.
+ * Refused before any launch: a NULL pointer (VV_ERR_NULL); batch <= 0, latent <= 0 or more than 2^31 - 1 elements, a rate
+ * that is NaN or outside [0, 1) (VV_ERR_SHAPE).  Pointers need float alignment and no more. */
+int vv_keep_mask(float *keep, int batch, int latent, float rate, unsigned long long seed, unsigned long long offset,
+                 void *hip_stream);
+int vv_keep_mask_host(float *keep, int batch, int latent, float rate, unsigned long long seed, unsigned long long offset);
+int vv_mask_scale(const float *x, const float *keep, float scale, float *y, int batch, int latent, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
