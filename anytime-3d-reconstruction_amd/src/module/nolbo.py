@@ -665,7 +665,8 @@ class nolboSingleObject_modelnet_category_only(_ModelnetBase):
     getEval with the prototype table replaced by the prior network's means over `category_indices` (nolbo.py:1685-1688).
     The prior network (a 40 -> ... -> L MLP, src/net_core/priornet.py) and the [B, L] latent algebra of fit() -- KL to the
     learned prior, prior / posterior mixing, the pairwise regulariser -- are outside the voxel path (SURVEY §8(f)
-    rank 2) and run as torch autograd code between the HIP encoder and decoder (voxvae.train.Trainer.step_custom_latent)."""
+    rank 2) and run by default as torch autograd code between the HIP encoder and decoder (voxvae.train.Trainer.step_custom_latent);
+    fit(latent='hip') puts the two launches of csrc/prior_latent.hip in the closure's place."""
     _variational = True
 
     def __init__(self, nolbo_structure,
@@ -681,10 +682,15 @@ class nolboSingleObject_modelnet_category_only(_ModelnetBase):
         self._priornet_class = priornet.priornet(structure=self._prior_class_str, device=self._device)
         self._trainer_c = None
 
-    def fit(self, inputs, dropout=False, *, _rand=None):
+    def fit(self, inputs, dropout=False, *, latent='torch', _rand=None):
         """nolbo.py:1620-1676: (x, y, onehot) -> (loss_kl, loss_shape, loss_reg, pr, rc); total = KL(q || prior) + shape +
-        0.01 reg.  `_rand` (tests) = dict(eps, eps_prior, mix (bool), noise [B,L], drop_rate, drop_keep [B,L])."""
+        0.01 reg.  `_rand` (tests) = dict(eps, eps_prior, mix (bool), noise [B,L], drop_rate, drop_keep [B,L]).
+        latent='torch' (the default): the latent algebra is the autograd closure below; latent='hip': ONE vv_prior_latent_train_fwd
+        and ONE vv_prior_latent_train_bwd stand in its place (voxvae.prior_latent.latent_stage), the dropout through vv_mask_scale
+        forward and on dz."""
         from voxvae import train as _T
+        if latent not in ('hip', 'torch'):
+            raise ValueError("latent must be 'hip' or 'torch', got %r" % (latent,))
         input_images, output_images, category_list = inputs
         x, y = self._dev_pair(input_images, output_images)
         onehot = self._dev(category_list)
@@ -709,7 +715,7 @@ class nolboSingleObject_modelnet_category_only(_ModelnetBase):
             drop = (keep, 1.0 / (1.0 - rate))
         dist = 2.0 * Lz
 
-        def latent(enc_out):
+        def latent_torch(enc_out):
             mean_p, lv_p = self._priornet_class(onehot, training=True)
             mean, lv = enc_out[:, :Lz], torch.clamp(enc_out[:, Lz:2 * Lz], -10.0, 10.0)
             z = mean + torch.sqrt(torch.exp(lv)) * eps                               # function.py:35-38
@@ -722,8 +728,17 @@ class nolboSingleObject_modelnet_category_only(_ModelnetBase):
             reg = torch.where(d > 0, torch.zeros_like(d), d * d).sum(-1).mean()      # function.py:40-71, no class input (:1663)
             return z_in, kl + 0.01 * reg, (kl.detach(), reg.detach())
 
+        def latent_hip(enc_out):
+            from voxvae import prior_latent as _PL
+            mean_p, lv_p = self._priornet_class(onehot, training=True)
+            z_in, extra, kl, reg, _ = _PL.latent_stage(enc_out, mean_p, lv_p, eps.contiguous(), eps_p.contiguous(),
+                                                       None if noise is None else noise.contiguous(), dist, 0.01)
+            if drop is not None:
+                z_in = _PL.mask_scale(z_in, drop[0].contiguous(), drop[1])
+            return z_in, extra, (kl.mean(), reg.mean())
+
         self._opt_prior.zero_grad(set_to_none=True)
-        stats, m, (kl, reg) = self._trainer_c.step_custom_latent(x, y, latent)
+        stats, m, (kl, reg) = self._trainer_c.step_custom_latent(x, y, latent_hip if latent == 'hip' else latent_torch)
         self._opt_prior.step()
         return DeviceArray(kl), DeviceArray(m[0]), DeviceArray(reg), DeviceArray(m[1]), DeviceArray(m[2])
 
@@ -985,3 +1000,218 @@ class nolboSingleObject_AE(nolboSingleObject_VAE):
             torch.autograd.backward([z] + reg, [dz if keep is None else dz * keep] + [torch.ones_like(t) for t in reg])
             self._opt2d.step()
         return DeviceArray(m[0]), DeviceArray(m[1]), DeviceArray(m[2])
+
+
+class _OnePriorImageModel(nolboSingleObject_VAE):
+    """What nolboSingleObject_instOnly and nolboSingleObject_category_only share: an image encoder that emits ONE latent group
+    ([mean | logVar]), ONE learned prior network over the sample's one-hot, and a fit whose span between the head output and the decoder
+    step (voxvae.train.Trainer.step_decoder) is ONE vv_prior_latent_train_fwd and, with the decoder's d shape / d z_in, ONE
+    vv_prior_latent_train_bwd (csrc/prior_latent.hip, through voxvae.prior_latent.latent_stage); the gradients continue through the 2D
+    encoder and the prior network by torch autograd.  The image encoder and the decoder are nolboSingleObject_VAE's.  A subclass names
+    its structure keys and the reference's constants."""
+    _z_key = None            # the latent's width in nolbo_structure['encoder_backbone']
+    _prior_key = None        # the prior network's structure in nolbo_structure
+    _prior_attr = None       # the attribute that holds the prior network
+    _dist_per_dim = None     # dist_in_z_space = _dist_per_dim * L
+    _reg_weight = None       # the regulariser's weight in the total loss
+    _network_l2 = None       # whether the sub-models' l2 terms are part of the total loss
+
+    def __init__(self, nolbo_structure, backbone_style=None, encoder_backbone=None, learning_rate=1e-4):
+        self._prior_str = nolbo_structure[self._prior_key]
+        setattr(self, '_%s_str' % self._prior_key, self._prior_str)        # the reference's name: _prior_inst_str / _prior_class_str
+        self._debug = None         # set to a dict to capture the latent stage's inputs and gradients of the next fit (tests)
+        nolboSingleObject_VAE.__init__(self, nolbo_structure, backbone_style=backbone_style, encoder_backbone=encoder_backbone,
+                                       dropout=False, learning_rate=learning_rate)
+
+    @property
+    def _latent_dim(self):
+        return self._enc_backbone_str[self._z_key]
+
+    def _buildModel(self):
+        nolboSingleObject_VAE._buildModel(self)
+        # ==============set prior network, under the reference's name (_priornet_inst / _priornet_class)
+        setattr(self, self._prior_attr, priornet.priornet(structure=self._prior_str, device=self._device))
+
+    @property
+    def _priornet(self):
+        return getattr(self, self._prior_attr)
+
+    def _latent_torch(self, e, pri, eps, eps_p, keep, dist):
+        """fit's latent algebra (function.py:35-38, 40-71, 84-98) as torch autograd code: what vv_prior_latent_train_fwd / _bwd compute,
+        kept as the comparison leg (latent='torch').  -> z_in [B, L], kl [B], reg [B]."""
+        Lz = self._latent_dim
+        mean_p, lv_p = pri
+        mean, lv = e[:, :Lz], torch.clamp(e[:, Lz:], -10.0, 10.0)
+        z = mean + torch.sqrt(torch.exp(lv)) * eps
+        z_prior = mean_p + torch.sqrt(torch.exp(lv_p)) * eps_p
+        z_in = z if keep is None else torch.where(keep == 1., z, z_prior)
+        kl = (0.5 * (lv_p - lv) + (torch.exp(lv) + (mean - mean_p) ** 2) / (2.0 * torch.exp(lv_p)) - 0.5).sum(-1)
+        d = (torch.abs(mean_p[:, None, :] - mean_p[None, :, :]) / torch.exp(0.5 * lv_p)[:, None, :]).sum(-1) - dist
+        return z_in, kl, torch.where(d > 0, torch.zeros_like(d), d * d).sum(-1)
+
+    def _decoder_input_keep(self, B, Lz, r):
+        """The step's draw of what the decoder sees: None = z; else keep [B, L], 1 where the element is z's, 0 where z_prior's."""
+        raise NotImplementedError
+
+    def fit(self, inputs, *, latent='hip', _rand=None):
+        from voxvae import prior_latent as _PL
+        from voxvae import train as _T
+        if latent not in ('hip', 'torch'):
+            raise ValueError("latent must be 'hip' or 'torch', got %r" % (latent,))
+        input_images, output_images, onehot = inputs
+        Lz = self._latent_dim
+        y, onehot = self._dev(output_images), self._dev(onehot).contiguous()
+        if getattr(self, '_trainer_p', None) is None:
+            self._trainer_p = _T.Trainer(None, self._dec_eng, variational=False, learning_rate=self._learning_rate)
+            mods = [m for m in (self._encoder_backbone, self._encoder_head, self._priornet) if isinstance(m, torch.nn.Module)]
+            self._opt_p = torch.optim.Adam([p for m in mods for p in m.parameters()], lr=self._learning_rate, eps=1e-7)   # Keras epsilon
+        self._opt_p.zero_grad(set_to_none=True)
+        pri = self._priornet(onehot, training=True)
+        enc_out = self._encoder_2d(input_images, training=True)
+        if not (torch.is_tensor(enc_out) and enc_out.requires_grad):                  # a 2D encoder without parameters, or head outputs
+            enc_out = self._dev(enc_out)
+        B = enc_out.shape[0]
+        if enc_out.dim() != 2 or enc_out.shape[1] != 2 * Lz:
+            raise ValueError('the encoder must emit [B, %d] (mean | logVar), got %s' % (2 * Lz, tuple(enc_out.shape)))
+        r = _rand or {}
+        eps, eps_p = self._draw_eps(B, r.get('eps')).contiguous(), self._draw_eps(B, r.get('eps_prior')).contiguous()
+        keep = self._decoder_input_keep(B, Lz, r)
+        dist = float(self._dist_per_dim) * Lz
+        l2 = []
+        if self._network_l2:
+            l2 = [l for m in (self._encoder_head, self._encoder_backbone, self._priornet) if hasattr(m, 'losses') for l in m.losses]
+            l2 = [torch.stack(l2).sum()] if l2 else []                               # the decoder's: step_decoder(l2=)
+        e = enc_out.detach().float().contiguous().requires_grad_(True)
+        twin = None
+        with torch.enable_grad():
+            if latent == 'torch':
+                z_in, kl, reg = self._latent_torch(e, pri, eps, eps_p, keep, dist)
+                extra = kl.mean() + self._reg_weight * reg.mean()
+            else:
+                z_in, extra, kl, reg, twin = _PL.latent_stage(e, pri[0], pri[1], eps, eps_p, keep, dist, self._reg_weight,
+                                                              bf16=self._act_dt != _L.VV_F32)
+        if self._debug is not None:
+            for t in pri:
+                if t.requires_grad:
+                    t.retain_grad()
+        _, m, dz = self._trainer_p.step_decoder(z_in.detach().contiguous(), y, z_act=twin, l2=ae3D.L2_REG if self._network_l2 else 0.0)
+        torch.autograd.backward([z_in, extra] + l2, [dz.contiguous(), torch.ones_like(extra)] + [torch.ones_like(t) for t in l2])
+        if enc_out.requires_grad:
+            enc_out.backward(e.grad)
+        self._opt_p.step()
+        if self._debug is not None:
+            self._debug.update({'enc_out': e.detach(), 'pri': [t.detach() for t in pri], 'keep': keep, 'z_in': z_in.detach(), 'dz_in': dz,
+                                'd_enc_out': e.grad, 'd_pri': [t.grad if t.requires_grad else None for t in pri], 'dist': dist,
+                                'reg_weight': self._reg_weight})
+        return DeviceArray(kl.detach().mean()), DeviceArray(m[0]), DeviceArray(reg.detach().mean()), DeviceArray(m[1]), DeviceArray(m[2])
+
+
+class nolboSingleObject_instOnly(_OnePriorImageModel):
+    """The reference's instance-only image model, nolbo.py:326-540 (train_kitti.py): one instance latent, a learned prior network over
+    the instance one-hot.  Structure keys as the reference's: encoder_backbone (z_inst_dim), encoder_head, decoder, prior_inst.
+    fit (:365-415): total = mean KL(q || prior) + shape + mean reg (dist 10 L) + the l2 terms of all four sub-models; the decoder sees z
+    or, with probability 1/2, z_prior for the whole batch.  getEval (:417-485): ONE vv_inst_latent_eval between the head output and the
+    two decoder passes."""
+    _z_key, _prior_key, _prior_attr = 'z_inst_dim', 'prior_inst', '_priornet_inst'
+    _dist_per_dim, _reg_weight, _network_l2 = 10.0, 1.0, True
+
+    def _decoder_input_keep(self, B, Lz, r):
+        """:383-386: `rand < 0.5` -> decoder(z), else decoder(z_prior); `_rand['from_prior']` (bool) injects the choice."""
+        from_prior = bool(r['from_prior']) if 'from_prior' in r else not (np.random.rand() < 0.5)
+        return torch.zeros(B, Lz, dtype=torch.float32, device=self._device) if from_prior else None
+
+    def fit(self, inputs, *, latent='hip', _rand=None):
+        """nolbo.py:365-415: (input_images, output_images, inst_list) -> (loss_kl, loss_shape, loss_reg, pr, rc).  latent='torch' runs
+        the same algebra as an autograd closure.  `_rand` (tests) = dict(eps, eps_prior [B, L], from_prior (bool))."""
+        return _OnePriorImageModel.fit(self, inputs, latent=latent, _rand=_rand)
+
+    def getEval(self, input_images, output_images, inst_list=np.identity(10), missing_prob=0.1, training=True, *, _eps=None, _mask=None,
+                _fill=None):
+        """reference nolbo.py:417-485 -> (pred, loss_shape, pr, rc, pred_corrected, loss_shape_corrected, pr_corrected, rc_corrected):
+        the decoder on z (masked elements replaced by an N(0,1) draw) and on the nearest instance prior's mean.  inst_list [I, I']: the
+        one-hots the prior table is made of.  `training` defaults to True as in the reference.  `_eps`, `_mask`, `_fill` [B, L] inject
+        the draws."""
+        from voxvae import prior_latent as _PL
+        prior, _ = self._priornet(np.asarray(inst_list, dtype=np.float32), training=bool(training))
+        prior = prior.detach().float().contiguous()
+        with torch.no_grad():
+            enc_out = self._enc_out(input_images, training=training).detach()
+        B, Lz = enc_out.shape[0], self._latent_dim
+        if enc_out.dim() != 2 or enc_out.shape[1] != 2 * Lz:
+            raise ValueError('the encoder must emit [B, %d] (mean | logVar), got %s' % (2 * Lz, tuple(enc_out.shape)))
+        y = self._dev(output_images)
+        eps = self._draw_eps(B, _eps).contiguous()
+        mask = fill = None
+        if missing_prob > 0:
+            mask = self._draw_mask(B, missing_prob, _mask, Lz).contiguous()             # :433-434, the same RNG call
+            fill = self._draw_eps(B, _fill).contiguous()                                # :438
+        twin = not training and self._act_dt != _L.VV_F32                              # training: float32 to the decoder entry (_eval_hooks)
+        z, zc, zb, zcb, idx = _PL.inst_eval(enc_out, eps, mask, fill, prior, bf16=twin)
+        decode = self._eval_hooks(training)[1]
+        pred, _, m = decode(zb if twin else z, y, None)                                # :443-449
+        pred_c, _, mc = decode(zcb if twin else zc, y, None)                           # :477-483
+        self._z, self._z_corrected, self._nearest = DeviceArray(z), DeviceArray(zc), DeviceArray(idx)
+        return self._scored(pred, m) + self._scored(pred_c, mc)
+
+    def savePriorInst(self, save_path):
+        self._priornet.save_weights(os.path.join(save_path, self._prior_str['name']))
+
+    def loadPriorInst(self, load_path, file_name=None):
+        self._priornet.load_weights(os.path.join(load_path, self._prior_str['name'] if file_name is None else file_name))
+
+    def saveModel(self, save_path):
+        self.saveEncoder(save_path)
+        self.saveDecoder(save_path)
+        self.savePriorInst(save_path)
+
+    def loadModel(self, load_path):
+        self.loadEncoder(load_path)
+        self.loadDecoder(load_path)
+        self.loadPriorInst(load_path)
+
+
+class nolboSingleObject_category_only(_OnePriorImageModel):
+    """The reference's category-only image model, nolbo.py:984-1204 (train_pascal_category.py, test_pascal_category.py): one category
+    latent, a learned prior network over the category one-hot.  Structure keys as the reference's: encoder_backbone (z_category_dim),
+    encoder_head, decoder, prior_class.  fit (:1023-1075): total = mean KL(q || prior) + shape + 0.01 mean reg (dist 3 L), no network l2
+    terms; the decoder sees z or, with probability 1/2, z with 30 % of its elements replaced by z_prior's.  getEval (:1077-1149) is
+    nolboSingleObject_VAE's with the prototype table replaced by the prior network's means over `category_indices`."""
+    _z_key, _prior_key, _prior_attr = 'z_category_dim', 'prior_class', '_priornet_class'
+    _dist_per_dim, _reg_weight, _network_l2 = 3.0, 0.01, False
+
+    def _decoder_input_keep(self, B, Lz, r):
+        """:1042-1047: `rand > 0.5` -> decoder(z), else keep ~ Bernoulli(0.7) per element (the same RNG call); `_rand['mix']` (bool) and
+        `_rand['noise']` [B, L] inject them."""
+        mix = bool(r['mix']) if 'mix' in r else not (np.random.rand() > 0.5)
+        if not mix:
+            return None
+        missing_pr = 0.3
+        return self._dev(r['noise'] if 'noise' in r else
+                         np.random.choice(a=[True, False], size=(B, Lz), p=[1. - missing_pr, missing_pr]).astype('float32')).contiguous()
+
+    def fit(self, inputs, *, latent='hip', _rand=None):
+        """nolbo.py:1023-1075: (input_images, output_images, category_list) -> (loss_kl, loss_shape, loss_reg, pr, rc).  latent='torch'
+        runs the same algebra as an autograd closure.  `_rand` (tests) = dict(eps, eps_prior [B, L], mix (bool), noise [B, L])."""
+        return _OnePriorImageModel.fit(self, inputs, latent=latent, _rand=_rand)
+
+    def getEval(self, inputs, category_indices=np.identity(12), training=False, missing_prob=0.0, *, _eps=None, _mask=None, _eps2=None):
+        """nolbo.py:1077-1149 -> the 10-tuple of the VAE class, classified / corrected against the prior means."""
+        mean_prior, _ = self._priornet(np.asarray(category_indices, dtype='float32'), training=bool(training))
+        return _ModelnetBase.getEval(self, inputs, category_vectors=mean_prior.detach().contiguous(), training=training,
+                                     missing_prob=missing_prob, _eps=_eps, _mask=_mask, _eps2=_eps2)
+
+    def savePriorCategory(self, save_path):
+        self._priornet.save_weights(os.path.join(save_path, self._prior_str['name']))
+
+    def loadPriorCategory(self, load_path, file_name=None):
+        self._priornet.load_weights(os.path.join(load_path, self._prior_str['name'] if file_name is None else file_name))
+
+    def saveModel(self, save_path):
+        self.saveEncoder(save_path)
+        self.saveDecoder(save_path)
+        self.savePriorCategory(save_path)
+
+    def loadModel(self, load_path):
+        self.loadEncoder(load_path)
+        self.loadDecoder(load_path)
+        self.loadPriorCategory(load_path)

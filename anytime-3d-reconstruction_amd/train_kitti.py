@@ -1,0 +1,101 @@
+"""Entry point mirroring the reference's train_kitti.py (loop :87-129, config :131-164): nolboSingleObject_instOnly.fit -- Darknet19 +
+head2D image encoder, an instance latent of 16, a prior network over the 10 instance one-hots, 64^3 decoder.  The reference reads
+KITTI crops through its KITTI loader; here the single-object loader of src/dataset_loader/pascal3D.py serves the same
+(inst_list, images, voxels) triple -- its seeded synthetic split by default.
+`python train_kitti.py --batch 16 --image 128 --max-iter 2`."""
+import sys
+
+import _entry_common as C
+import voxvae
+import src.dataset_loader.pascal3D as pascal3D
+import src.net_core.darknet as Darknet
+
+INSTANCES = 10
+
+
+def make_config(latent_dim=16, voxel=64, instances=INSTANCES):
+    return {
+        'encoder_backbone': {'name': 'nolbo_backbone', 'z_inst_dim': latent_dim, 'activation': 'elu'},
+        'encoder_head': {'name': 'nolbo_head', 'output_dim': 2 * latent_dim, 'filter_num_list': [], 'filter_size_list': [],
+                         'activation': 'elu'},
+        'decoder': C.make_config(latent_dim, voxel, True)['decoder'],
+        'prior_inst': {'name': 'priornet_inst', 'input_dim': instances, 'unit_num_list': [32, latent_dim], 'core_activation': 'elu',
+                       'const_log_var': 0.0},
+    }
+
+
+def inputs_of(batch):
+    """The loader's positional tuple -> the model's (images, voxels, instance one-hots)."""
+    inst_list, input_images, output_images = batch[0], batch[-2], batch[-1]
+    return input_images, output_images, inst_list
+
+
+def train(
+        training_epoch=1000,
+        learning_rate=1e-4,
+        config=None,
+        save_path=None, load_path=None,
+        load_encoder_backbone_path=None, load_encoder_backbone_name=None,
+        load_decoder_path=None, load_decoder_name=None,
+        batch_size=72, image_size=(256, 256), max_iter=None, dataset_path=None,
+):
+    import src.module.nolbo as nolbo
+    model = nolbo.nolboSingleObject_instOnly(nolbo_structure=config, backbone_style=Darknet.Darknet19, learning_rate=learning_rate)
+    loader = pascal3D.dataLoaderSingleObject(trainOrVal='train', Pascal3DDataPath=dataset_path, voxel=config['decoder']['output_shape'][0],
+                                             instances=config['prior_inst']['input_dim'])
+    if load_path is not None:
+        print('load weights...')
+        model.loadModel(load_path=load_path)
+        print('done!')
+    if load_encoder_backbone_path is not None:
+        model.loadEncoderBackbone(load_path=load_encoder_backbone_path, file_name=load_encoder_backbone_name)
+    if load_decoder_path is not None:
+        model.loadDecoder(load_path=load_decoder_path, file_name=load_decoder_name)
+
+    means = C.RunningMeans(fit=5)
+    bar = C.Progress(width=4)
+
+    def on_new_epoch():
+        print('')
+        means.reset()
+        bar.reset()
+        if save_path is not None:
+            print('save model...')
+            model.saveModel(save_path=save_path)
+
+    print('start training...')
+    for epoch, position, total in C.epochs_of(loader, training_epoch, 'dataStart', on_new_epoch):
+        bar.tic()
+        inputs = inputs_of(loader.getNextBatch(batchSizeof3DShape=batch_size, imageSize=image_size))
+        means.add(fit=model.fit(inputs=inputs))
+        bar.toc()
+        bar.show(epoch, position, total, bar.group(zip(('kl', 'shape', 'reg', 'pr', 'rc'), means['fit'])))
+        if C.stop_on_nan(means):
+            return None
+        if max_iter is not None and means.n >= max_iter:
+            break
+    print('')
+    return means['fit']
+
+
+latent_dim = 16
+config = make_config(latent_dim, 64)
+
+if __name__ == '__main__':
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument('--voxel', type=int, default=64)
+    ap.add_argument('--latent', type=int, default=16)
+    ap.add_argument('--batch', type=int, default=72)
+    ap.add_argument('--image', type=int, default=256)
+    ap.add_argument('--epochs', type=int, default=1000)
+    ap.add_argument('--lr', type=float, default=1e-4)
+    ap.add_argument('--save-path', default=None)
+    ap.add_argument('--load-path', default=None)
+    ap.add_argument('--max-iter', type=int, default=None)
+    ap.add_argument('--dataset-path', default=None)
+    a = ap.parse_args()
+    voxvae.set_default_dtype('f32')        # the 2D encoder trains by float32 autograd
+    sys.exit(0 if train(training_epoch=a.epochs, learning_rate=a.lr, config=make_config(a.latent, a.voxel), save_path=a.save_path,
+                        load_path=a.load_path, batch_size=a.batch, image_size=(a.image, a.image), max_iter=a.max_iter,
+                        dataset_path=a.dataset_path) is not None else 1)

@@ -1,0 +1,102 @@
+"""Entry point mirroring the reference's train_pascal_category.py (loop :118-171, config :173-206): nolboSingleObject_category_only.fit
+on the training split, getEval on the same batch and on a validation batch -- Darknet19 + head2D image encoder, a category latent of
+16, a prior network over the 12 categories, 64^3 decoder.
+`python train_pascal_category.py --batch 16 --image 128 --max-iter 2`."""
+import sys
+
+import _entry_common as C
+import voxvae
+import src.dataset_loader.pascal3D as pascal3D
+import src.net_core.darknet as Darknet
+
+
+def make_config(latent_dim=16, voxel=64):
+    return {
+        'encoder_backbone': {'name': 'nolbo_backbone', 'z_category_dim': latent_dim, 'activation': 'elu'},
+        'encoder_head': {'name': 'nolbo_head', 'output_dim': 2 * latent_dim, 'filter_num_list': [], 'filter_size_list': [],
+                         'activation': 'elu'},
+        'decoder': C.make_config(latent_dim, voxel, True)['decoder'],
+        'prior_class': {'name': 'priornet_class', 'input_dim': pascal3D.CLASSES, 'unit_num_list': [32, latent_dim], 'core_activation': 'elu',
+                        'const_log_var': 0.0},
+    }
+
+
+def inputs_of(batch):
+    """The loader's positional tuple -> the model's (images, voxels, category one-hots)."""
+    _, category_list, _, _, input_images, output_images = batch
+    return input_images, output_images, category_list
+
+
+def train(
+        training_epoch=1000,
+        learning_rate=1e-4,
+        config=None,
+        save_path=None, load_path=None,
+        load_encoder_backbone_path=None, load_encoder_backbone_name=None,
+        load_decoder_path=None, load_decoder_name=None,
+        batch_size=72, image_size=(256, 256), max_iter=None, dataset_path=None,
+):
+    import src.module.nolbo as nolbo
+    model = nolbo.nolboSingleObject_category_only(nolbo_structure=config, backbone_style=Darknet.Darknet19, learning_rate=learning_rate)
+    voxel = config['decoder']['output_shape'][0]
+    loader = pascal3D.dataLoaderSingleObject(trainOrVal='train', Pascal3DDataPath=dataset_path, voxel=voxel)
+    loader_test = pascal3D.dataLoaderSingleObject(trainOrVal='val', Pascal3DDataPath=dataset_path, voxel=voxel)
+    if load_path is not None:
+        print('load weights...')
+        model.loadModel(load_path=load_path)
+        print('done!')
+    if load_encoder_backbone_path is not None:
+        model.loadEncoderBackbone(load_path=load_encoder_backbone_path, file_name=load_encoder_backbone_name)
+    if load_decoder_path is not None:
+        model.loadDecoder(load_path=load_decoder_path, file_name=load_decoder_name)
+
+    means = C.RunningMeans(fit=5, train=9, test=9)
+    bar = C.Progress(width=4)
+
+    def on_new_epoch():
+        print('')
+        means.reset()
+        bar.reset()
+        if save_path is not None:
+            print('save model...')
+            model.saveModel(save_path=save_path)
+
+    print('start training...')
+    for epoch, position, total in C.epochs_of(loader, training_epoch, 'dataStart', on_new_epoch):
+        bar.tic()
+        inputs = inputs_of(loader.getNextBatch(batchSizeof3DShape=batch_size, imageSize=image_size))
+        inputs_test = inputs_of(loader_test.getNextBatch(batchSizeof3DShape=batch_size, imageSize=image_size, augmentation=False))
+        means.add(fit=model.fit(inputs=inputs), train=model.getEval(inputs=inputs)[1:], test=model.getEval(inputs=inputs_test)[1:])
+        bar.toc()
+        f, tr, te = means['fit'], means['train'], means['test']
+        bar.show(epoch, position, total, bar.group(zip(('kl', 'shape', 'reg', 'pr', 'rc'), f)) + ", " + bar.group([('c', tr[3])]),
+                 bar.group(zip(('shape', 'pr', 'rc', 'c'), te[:4])))
+        if C.stop_on_nan(means):
+            return None
+        if max_iter is not None and means.n >= max_iter:
+            break
+    print('')
+    return means['fit']
+
+
+latent_dim = 16
+config = make_config(latent_dim, 64)
+
+if __name__ == '__main__':
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument('--voxel', type=int, default=64)
+    ap.add_argument('--latent', type=int, default=16)
+    ap.add_argument('--batch', type=int, default=72)
+    ap.add_argument('--image', type=int, default=256)
+    ap.add_argument('--epochs', type=int, default=1000)
+    ap.add_argument('--lr', type=float, default=1e-4)
+    ap.add_argument('--save-path', default=None)
+    ap.add_argument('--load-path', default=None)
+    ap.add_argument('--max-iter', type=int, default=None)
+    ap.add_argument('--dataset-path', default=None)
+    a = ap.parse_args()
+    voxvae.set_default_dtype('f32')        # the 2D encoder trains by float32 autograd
+    sys.exit(0 if train(training_epoch=a.epochs, learning_rate=a.lr, config=make_config(a.latent, a.voxel), save_path=a.save_path,
+                        load_path=a.load_path, batch_size=a.batch, image_size=(a.image, a.image), max_iter=a.max_iter,
+                        dataset_path=a.dataset_path) is not None else 1)

@@ -116,6 +116,12 @@ SIGNATURES = {
     'vv_mm_latent_train_fwd_host': (_i, [_vp] * 11 + [_i, _vp, _vp] + [_i] * 4),
     'vv_mm_latent_train_bwd': (_i, [_vp] * 10 + [_f] + [_vp] * 5 + [_i] * 4 + [_vp]),
     'vv_mm_latent_train_bwd_host': (_i, [_vp] * 10 + [_f] + [_vp] * 5 + [_i] * 4),
+    'vv_prior_latent_train_fwd': (_i, [_vp] * 6 + [_f] + [_vp] * 4 + [_i, _i, _vp]),
+    'vv_prior_latent_train_fwd_host': (_i, [_vp] * 6 + [_f] + [_vp] * 4 + [_i, _i]),
+    'vv_prior_latent_train_bwd': (_i, [_vp] * 6 + [_f, _vp, _f, _f] + [_vp] * 3 + [_i, _i, _vp]),
+    'vv_prior_latent_train_bwd_host': (_i, [_vp] * 6 + [_f, _vp, _f, _f] + [_vp] * 3 + [_i, _i]),
+    'vv_inst_latent_eval': (_i, [_vp] * 10 + [_i, _i, _i, _vp]),
+    'vv_inst_latent_eval_host': (_i, [_vp] * 10 + [_i, _i, _i]),
     'vv_conv2d_packed_bytes': (_sz, [_i, _i, _i, _i]),
     'vv_pack_conv2d': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'vv_conv2d_supported': (_i, [_i] * 5),

@@ -550,6 +550,58 @@ int vv_mm_latent_train_bwd_host(const float *enc_out, const float *eps, const fl
                                 int batch, int lc, int li, int classes);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * The latent stage of the models with ONE latent group and ONE learned prior: nolboSingleObject_instOnly (src/module/nolbo.py:326-540),
+ * nolboSingleObject_category_only (:984-1204) and nolboSingleObject_modelnet_category_only (:1594-1787).  enc_out float32 [B, 2 L] =
+ * [mean | logVar]; every other array is float32 [B, L] unless stated.  1 <= L <= 64; B >= 1; 1 <= insts <= 256; else VV_ERR_SHAPE.
+ * NULL and shape checks come before any launch.  Pointers need the alignment of their element type and no more.  The arithmetic is
+ * csrc/prior_latent.h on the scalar helpers of csrc/mm_latent.h: float32, exp from csrc/detect_decode.h, correctly rounded division and
+ * square root, no contraction, no atomics, EVERY sum in ascending index order (over l, over the prior table's rows, over the batch j)
+ * -- the same bits on every run, and the *_host entries (the same header in loops on the CPU, host pointers, no stream) agree with the
+ * device entries bit for bit.  There is no dtype argument: a bfloat16 twin (round to nearest even) is written where its pointer is
+ * given.
+ *
+ * vv_prior_latent_train_fwd  (fit, nolbo.py:365-403, :1023-1063; one launch: a wave per sample, the batch walked in pieces through LDS)
+ *   mean_p, lv_p        the prior network's outputs for each sample, not clipped;  eps, eps_p: the posterior's and the prior's draws
+ *   keep                in {0,1} or NULL;  dist: dist_in_z_space (10 L for instOnly, 3 L for category_only)
+ *   z = mean + sqrt(exp(clip(logVar, -10, 10))) eps;  z_prior = mean_p + sqrt(exp(lv_p)) eps_p
+ *   z_in                keep NULL: z; else where(keep == 1, z, z_prior) (:1047) -- all zeros: instOnly's decoder(z_prior) branch (:386)
+ *   z_in_bf16           optional twin of z_in
+ *   kl [B]              kl_loss against the given prior (function.py:84-98)
+ *   reg [B]             regulizer_loss(mean_p, lv_p, dist) without a class input (function.py:40-71): d_ij = sum_l |m_i - m_j|_l /
+ *                       exp(0.5 lv_i)_l - dist;  reg_i = sum_j (d_ij <= 0 ? d_ij^2 : 0) over j ascending, j = i included
+ * vv_prior_latent_train_bwd  (one launch): for total = mean_b kl + reg_weight mean_b reg + shape, with dz_in = d shape / d z_in and
+ *   inv_batch = 1 / B, writes d_enc_out [B, 2 L], d_mean_p and d_lv_p (each of the last two may be NULL: a constant log-variance has no
+ *   gradient).  dz_in goes to the posterior where the element took z and to the prior where it took z_prior.  A log-variance gradient
+ *   passes the clip where -10 <= raw <= 10 (as vv_reparam_kl_bwd); d|x|/dx at 0 is 0; row i receives the (i, j) and the (j, i) pairs,
+ *   summed over j in ascending order. */
+int vv_prior_latent_train_fwd(const float *enc_out, const float *eps, const float *mean_p, const float *lv_p, const float *eps_p,
+                              const float *keep, float dist, float *z_in, void *z_in_bf16, float *kl, float *reg, int batch, int latent,
+                              void *hip_stream);
+int vv_prior_latent_train_fwd_host(const float *enc_out, const float *eps, const float *mean_p, const float *lv_p, const float *eps_p,
+                                   const float *keep, float dist, float *z_in, void *z_in_bf16, float *kl, float *reg, int batch,
+                                   int latent);
+int vv_prior_latent_train_bwd(const float *enc_out, const float *eps, const float *mean_p, const float *lv_p, const float *eps_p,
+                              const float *keep, float dist, const float *dz_in, float inv_batch, float reg_weight, float *d_enc_out,
+                              float *d_mean_p, float *d_lv_p, int batch, int latent, void *hip_stream);
+int vv_prior_latent_train_bwd_host(const float *enc_out, const float *eps, const float *mean_p, const float *lv_p, const float *eps_p,
+                                   const float *keep, float dist, const float *dz_in, float inv_batch, float reg_weight,
+                                   float *d_enc_out, float *d_mean_p, float *d_lv_p, int batch, int latent);
+/* vv_inst_latent_eval  (instOnly.getEval, nolbo.py:417-485; one launch: a workgroup per sample)
+ *   mask in {0,1} or NULL (missing_prob == 0);  fill: the N(0,1) draw of :438, required exactly when mask is given (a mismatch is
+ *                       VV_ERR_NULL)
+ *   prior [insts, L]    the instance prior's means
+ *   z                   the sample; with a mask z mask, and every element that compares equal to 0 -- an unmasked +-0 too -- takes
+ *                       fill (:435-439)
+ *   idx int32 [B]       first argmin over i of sum_l mask_l (z - prior_i)_l^2 (:460-462; the mask counts as ones when NULL).  Only
+ *                       distances below +inf compete; a row that has none gets 0.
+ *   z_corr              prior[idx], the whole row (:474)
+ *   z_bf16, z_corr_bf16 optional twins */
+int vv_inst_latent_eval(const float *enc_out, const float *eps, const float *mask, const float *fill, const float *prior, float *z,
+                        float *z_corr, void *z_bf16, void *z_corr_bf16, int *idx, int batch, int latent, int insts, void *hip_stream);
+int vv_inst_latent_eval_host(const float *enc_out, const float *eps, const float *mask, const float *fill, const float *prior, float *z,
+                             float *z_corr, void *z_bf16, void *z_corr_bf16, int *idx, int batch, int latent, int insts);
+
+/* ---------------------------------------------------------------------------------------------------------
  * The image encoder: Darknet19 and head2D (src/net_core/darknet.py:83-94 Darknet19Conv, :96-133 the backbone, :135-168 convHead /
  * head2D) as channels-last 2D layers.  Here grids are NOT cubic and NOT powers of two: x [B,R,C,Cin], any batch, rows, cols >= 1.
  *
