@@ -34,9 +34,54 @@ def _st():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _sample_kl_torch(mean, lv, mean_p, lv_p, eps, eps_p, take_z):
+    """Sampling | prior / posterior choice | KL(q || prior) (function.py:35-38, 84-98) as torch autograd code: the comparison leg
+    (latent='torch') of the HIP latent stages.  take_z: None (z itself) or bool [B, L], False where z_prior stands in -> z_in [B, L], kl [B]."""
+    z = mean + torch.sqrt(torch.exp(lv)) * eps
+    z_prior = mean_p + torch.sqrt(torch.exp(lv_p)) * eps_p
+    z_in = z if take_z is None else torch.where(take_z, z, z_prior)
+    return z_in, (0.5 * (lv_p - lv) + (torch.exp(lv) + (mean - mean_p) ** 2) / (2.0 * torch.exp(lv_p)) - 0.5).sum(-1)
+
+
+def _pair_reg_torch(mean_p, lv_p, dist, cls=None):
+    """The pairwise regulariser of a prior's outputs (function.py:40-71) -> [B]; cls [B, C]: only pairs of one class count."""
+    d = (torch.abs(mean_p[:, None, :] - mean_p[None, :, :]) / torch.exp(0.5 * lv_p)[:, None, :]).sum(-1) - dist
+    v = torch.where(d > 0, torch.zeros_like(d), d * d)
+    if cls is not None:
+        v = v * (torch.abs(cls[:, None, :] - cls[None, :, :]).sum(-1) <= 0).to(v.dtype)
+    return v.sum(-1)
+
+
+def _one_prior_latent_torch(e, pri, eps, eps_p, keep, dist):
+    """The latent algebra of the models with ONE learned prior: what vv_prior_latent_train_fwd / _bwd compute.  e [B, 2L] = (mean | logVar),
+    pri = the prior's (mean, logVar), keep None or [B, L] (1: the element is z's, else z_prior's) -> z_in [B, L], kl [B], reg [B]."""
+    Lz = e.shape[1] // 2
+    z_in, kl = _sample_kl_torch(e[:, :Lz], torch.clamp(e[:, Lz:], -10.0, 10.0), *pri, eps, eps_p, None if keep is None else keep == 1.)
+    return z_in, kl, _pair_reg_torch(*pri, dist)
+
+
+def _prior_checkpoints(cls):
+    """Class decorator: the reference's savePrior<X> / loadPrior<X> for every (network attribute, structure attribute, X) of cls._priors;
+    _ModelnetBase.saveModel / loadModel call them."""
+    def add(net, structure, suffix):
+        def save(self, save_path):
+            getattr(self, net).save_weights(os.path.join(save_path, getattr(self, structure)['name']))
+
+        def load(self, load_path, file_name=None):
+            getattr(self, net).load_weights(os.path.join(load_path, file_name or getattr(self, structure)['name']))
+
+        setattr(cls, 'savePrior' + suffix, save)
+        setattr(cls, 'loadPrior' + suffix, load)
+
+    for entry in cls._priors:
+        add(*entry)
+    return cls
+
+
 class _ModelnetBase(object):
     _variational = True
     _keep_masks = None      # voxvae.mask_source() == 'device' when the model was built: its voxvae.masks.KeepMasks stream
+    _priors = ()            # the learned prior networks: ((network attribute, structure attribute, X of savePrior<X>), ...)
 
     @property
     def _latent_dim(self):
@@ -63,6 +108,31 @@ class _ModelnetBase(object):
     def _draw_keep(self, B, Lz, rate):
         """The device source's dropout mask [B, L] for this step, or None where the host draws it."""
         return None if self._keep_masks is None else self._keep_masks.dropout(B, Lz, rate)
+
+    def _draw_dropout(self, B, Lz, rate=None, keep=None):
+        """One step's inverted dropout on the latent (reference nolbo.py:586-588, 1423-1425) -> (keep [B, L] on the device, 1 / (1 - rate)):
+        the rate ~ U[0,1) from np.random unless injected; the keep injected, else the model's KeepMasks stream when the masks are drawn on
+        the device, else torch.rand(...) >= rate."""
+        rate = float(np.random.rand()) if rate is None else float(rate)
+        keep = self._draw_keep(B, Lz, rate) if keep is None else self._dev(keep)
+        keep = (torch.rand(B, Lz, device=self._device) >= rate).float() if keep is None else keep
+        return keep, 1.0 / (1.0 - rate)
+
+    def _draw_mix(self, B, Lz, r, a=(True, False), missing_pr=0.3):
+        """A training step's draw of what the decoder sees (nolbo.py:1042-1047, 1642-1647; :119-122 with a = (False, True) and 0.5):
+        `rand > 0.5` -> None (z itself), else a [B, L] selector drawn per element from `a` with probabilities (1 - missing_pr, missing_pr)
+        -- the category-only models' keep, 0 where z_prior stands in (the same RNG calls); `r['mix']` (bool) and `r['noise']` [B, L]
+        inject them."""
+        mix = bool(r['mix']) if 'mix' in r else not (np.random.rand() > 0.5)
+        if not mix:
+            return None
+        return self._dev(r['noise'] if 'noise' in r else
+                         np.random.choice(a=list(a), size=(B, Lz), p=[1. - missing_pr, missing_pr]).astype('float32')).contiguous()
+
+    @staticmethod
+    def _check_width(enc_out, width, layout):
+        if enc_out.dim() != 2 or enc_out.shape[1] != width:
+            raise ValueError('the encoder must emit [B, %d] (%s), got %s' % (width, layout, tuple(enc_out.shape)))
 
     # ---------------------------------------------------------------- device-side building blocks
     def _dev(self, a):
@@ -96,8 +166,7 @@ class _ModelnetBase(object):
         """(mean | logVar) [B,2L] -> slice | clip | sampling | KL (nolbo.py:1417-1420, 1464-1470) through vv_reparam_kl_fwd.
         Returns (z, z_act, kl, mean, clipped logVar), the last two None without want_stats."""
         Lz = self._latent_dim
-        if enc_out.dim() != 2 or enc_out.shape[1] != 2 * Lz:
-            raise ValueError('the encoder must emit [B, %d] (mean | logVar), got %s' % (2 * Lz, tuple(enc_out.shape)))
+        self._check_width(enc_out, 2 * Lz, 'mean | logVar')
         return _E.reparam_kl(enc_out, self._draw_eps(enc_out.shape[0], eps), Lz, self._act_dt if act_dt is None else act_dt,
                              want_stats=want_stats)
 
@@ -464,6 +533,8 @@ class _ModelnetBase(object):
     def saveModel(self, save_path):
         self.saveEncoder(save_path=save_path)
         self.saveDecoder(save_path=save_path)
+        for p in self._priors:
+            getattr(self, 'savePrior' + p[2])(save_path=save_path)
 
     def loadEncoder(self, load_path, file_name=None):
         if file_name == None:
@@ -478,6 +549,8 @@ class _ModelnetBase(object):
     def loadModel(self, load_path):
         self.loadEncoder(load_path=load_path)
         self.loadDecoder(load_path=load_path)
+        for p in self._priors:
+            getattr(self, 'loadPrior' + p[2])(load_path=load_path)
 
 
 class nolboSingleObject_modelnet_category_AE(_ModelnetBase):
@@ -601,36 +674,48 @@ class nolboSingleObject_VAE(_ModelnetBase):
             a = a.numpy()
         return as_device_f32(a, self._device)
 
+    # ---------------------------------------------------------------- what the fits of the image family share
+    def _image_trainer(self, variational=False):
+        """(the decoder's Trainer, torch Adam over whichever of backbone, head and prior networks are torch modules -- None without
+        parameters), built by the first fit."""
+        if self._trainer2d is None:
+            from voxvae import train as _T
+            self._trainer2d = _T.Trainer(None, self._dec_eng, variational=variational, learning_rate=self._learning_rate)
+            mods = [self._encoder_backbone, self._encoder_head] + [getattr(self, p[0]) for p in self._priors]
+            params = [p for m in mods if isinstance(m, torch.nn.Module) for p in m.parameters()]
+            self._opt2d = torch.optim.Adam(params, lr=self._learning_rate, eps=1e-7) if params else None   # Keras epsilon
+        return self._trainer2d, self._opt2d
+
+    def _l2_terms(self):
+        """The l2 terms of head, backbone and prior networks as a list of their one sum, [] without any (the decoder's: the trainer's l2=)."""
+        l2 = [l for m in [self._encoder_head, self._encoder_backbone] + [getattr(self, p[0]) for p in self._priors] if hasattr(m, 'losses')
+              for l in m.losses]
+        return [torch.stack(l2).sum()] if l2 else []
+
+    def _head_output_training(self, input_images):
+        """The 2D encoder's output in training mode; one without a graph (no parameters, or head outputs fed in) is moved to the device."""
+        enc_out = self._encoder_2d(input_images, training=True)
+        return enc_out if torch.is_tensor(enc_out) and enc_out.requires_grad else self._dev(enc_out)
+
     def fit(self, inputs, _eps=None, _dropout=None):
         """nolbo.py:786-833: (input_images, output_images) -> (loss_kl, loss_shape, pr, rc).  total = KL + shape + the l2
         terms of the 2D head; Adam(learning_rate) on backbone + head (torch) and decoder (HIP)."""
-        from voxvae import train as _T
         input_images, output_images = inputs
         y = self._dev(output_images)
-        if self._trainer2d is None:
-            self._trainer2d = _T.Trainer(None, self._dec_eng, variational=True, learning_rate=self._learning_rate)
-            mods = [m for m in (self._encoder_backbone, self._encoder_head) if isinstance(m, torch.nn.Module)]
-            params = [p for m in mods for p in m.parameters()]
-            self._opt2d = torch.optim.Adam(params, lr=self._learning_rate, eps=1e-7) if params else None   # Keras epsilon
-        trainable_2d = self._opt2d is not None
-        enc_out = self._encoder_2d(input_images, training=True) if trainable_2d else self._dev(self._encoder_2d(input_images))
-        B, Lz = enc_out.shape[0], self._latent_dim
+        trainer, opt = self._image_trainer(variational=True)
+        enc_out = self._encoder_2d(input_images, training=True) if opt is not None else self._dev(self._encoder_2d(input_images))
+        B = enc_out.shape[0]
         eps = self._draw_eps(B, _eps)
-        drop_mask, drop_scale = None, 1.0
-        if self._dropout:
-            rate, keep = _dropout if _dropout is not None else (float(np.random.rand()), None)
-            keep = self._draw_keep(B, Lz, rate) if keep is None else self._dev(keep)
-            keep = (torch.rand(B, Lz, device=self._device) >= rate).float() if keep is None else keep
-            drop_mask, drop_scale = keep, 1.0 / (1.0 - rate)
-        kl, stats, metrics, de = self._trainer2d.step_from_latent(enc_out.detach().contiguous(), y, eps, drop_mask, drop_scale,
-                                                                   l2=ae3D.L2_REG)      # + decoder.losses, nolbo.py:819-823
-        if trainable_2d:
-            self._opt2d.zero_grad(set_to_none=True)
-            reg = [l for m in (self._encoder_head, self._encoder_backbone) if hasattr(m, 'losses') for l in m.losses]
+        drop_mask, drop_scale = self._draw_dropout(B, self._latent_dim, *(_dropout or ())) if self._dropout else (None, 1.0)
+        kl, stats, metrics, de = trainer.step_from_latent(enc_out.detach().contiguous(), y, eps, drop_mask, drop_scale,
+                                                          l2=ae3D.L2_REG)               # + decoder.losses, nolbo.py:819-823
+        if opt is not None:
+            opt.zero_grad(set_to_none=True)
+            reg = self._l2_terms()
             enc_out.backward(de, retain_graph=bool(reg))
-            if reg:
-                torch.stack(reg).sum().backward()
-            self._opt2d.step()
+            for t in reg:
+                t.backward()
+            opt.step()
         m = metrics.cpu().numpy()
         return float(kl.mean().item()), float(m[0]), float(m[1]), float(m[2])
 
@@ -659,6 +744,7 @@ class nolboSingleObject_VAE(_ModelnetBase):
         self.loadEncoderHead(load_path)
 
 
+@_prior_checkpoints
 class nolboSingleObject_modelnet_category_only(_ModelnetBase):
     """reference nolbo.py:1594-1787: the VAE with a learned class-conditional prior.  Encoder, decoder, losses and the
     missing-latent correction run on the HIP path as in nolboSingleObject_modelnet_category_VAE -- getEval is that class's
@@ -668,6 +754,7 @@ class nolboSingleObject_modelnet_category_only(_ModelnetBase):
     rank 2) and run by default as torch autograd code between the HIP encoder and decoder (voxvae.train.Trainer.step_custom_latent);
     fit(latent='hip') puts the two launches of csrc/prior_latent.hip in the closure's place."""
     _variational = True
+    _priors = (('_priornet_class', '_prior_class_str', 'Category'),)
 
     def __init__(self, nolbo_structure,
                  learning_rate=1e-4):
@@ -699,40 +786,22 @@ class nolboSingleObject_modelnet_category_only(_ModelnetBase):
             self._trainer_c = _T.Trainer(self._enc_eng, self._dec_eng, variational=False, learning_rate=self._learning_rate)
             self._opt_prior = torch.optim.Adam(self._priornet_class.parameters(), lr=self._learning_rate, eps=1e-7)
         r = _rand or {}
-        dev = self._device
-        eps, eps_p = self._draw_eps(B, r.get('eps')), self._draw_eps(B, r.get('eps_prior'))
-        mix = bool(r['mix']) if 'mix' in r else not (np.random.rand() > 0.5)       # :1642: z itself with probability 1/2
-        noise = None
-        if mix:
-            missing_pr = 0.3
-            noise = self._dev(r['noise']) if 'noise' in r else self._dev(
-                np.random.choice(a=[True, False], size=(B, Lz), p=[1. - missing_pr, missing_pr]).astype('float32'))
-        drop = None
-        if dropout:
-            rate = float(r.get('drop_rate', np.random.rand()))
-            keep = self._dev(r['drop_keep']) if 'drop_keep' in r else self._draw_keep(B, Lz, rate)
-            keep = (torch.rand(B, Lz, device=dev) >= rate).float() if keep is None else keep
-            drop = (keep, 1.0 / (1.0 - rate))
+        eps, eps_p = self._draw_eps(B, r.get('eps')).contiguous(), self._draw_eps(B, r.get('eps_prior')).contiguous()
+        noise = self._draw_mix(B, Lz, r)                                       # :1642: z itself with probability 1/2
+        drop = self._draw_dropout(B, Lz, r.get('drop_rate'), r.get('drop_keep')) if dropout else None
         dist = 2.0 * Lz
 
         def latent_torch(enc_out):
-            mean_p, lv_p = self._priornet_class(onehot, training=True)
-            mean, lv = enc_out[:, :Lz], torch.clamp(enc_out[:, Lz:2 * Lz], -10.0, 10.0)
-            z = mean + torch.sqrt(torch.exp(lv)) * eps                               # function.py:35-38
-            z_prior = mean_p + torch.sqrt(torch.exp(lv_p)) * eps_p
-            z_in = z if noise is None else torch.where(noise == 1., z, z_prior)
+            z_in, kl, reg = _one_prior_latent_torch(enc_out, self._priornet_class(onehot, training=True), eps, eps_p, noise, dist)
             if drop is not None:
                 z_in = z_in * drop[0] * drop[1]
-            kl = (0.5 * (lv_p - lv) + (torch.exp(lv) + (mean - mean_p) ** 2) / (2.0 * torch.exp(lv_p)) - 0.5).sum(-1).mean()   # function.py:84-98
-            d = (torch.abs(mean_p[:, None, :] - mean_p[None, :, :]) / torch.exp(0.5 * lv_p)[:, None, :]).sum(-1) - dist
-            reg = torch.where(d > 0, torch.zeros_like(d), d * d).sum(-1).mean()      # function.py:40-71, no class input (:1663)
+            kl, reg = kl.mean(), reg.mean()                                           # function.py:84-98; :40-71, no class input (:1663)
             return z_in, kl + 0.01 * reg, (kl.detach(), reg.detach())
 
         def latent_hip(enc_out):
             from voxvae import prior_latent as _PL
             mean_p, lv_p = self._priornet_class(onehot, training=True)
-            z_in, extra, kl, reg, _ = _PL.latent_stage(enc_out, mean_p, lv_p, eps.contiguous(), eps_p.contiguous(),
-                                                       None if noise is None else noise.contiguous(), dist, 0.01)
+            z_in, extra, kl, reg, _ = _PL.latent_stage(enc_out, mean_p, lv_p, eps, eps_p, noise, dist, 0.01)
             if drop is not None:
                 z_in = _PL.mask_scale(z_in, drop[0].contiguous(), drop[1])
             return z_in, extra, (kl.mean(), reg.mean())
@@ -749,49 +818,94 @@ class nolboSingleObject_modelnet_category_only(_ModelnetBase):
         return _ModelnetBase.getEval(self, inputs, category_vectors=mean_prior.detach().contiguous(), training=training,
                                      missing_prob=missing_prob, _eps=_eps, _mask=_mask, _eps2=_eps2)
 
-    def savePriorCategory(self, save_path):
-        self._priornet_class.save_weights(os.path.join(save_path, self._prior_class_str['name']))
 
-    def loadPriorCategory(self, load_path, file_name=None):
-        self._priornet_class.load_weights(os.path.join(load_path, file_name or self._prior_class_str['name']))
+class _PriorImageModel(nolboSingleObject_VAE):
+    """The image models with learned prior networks: the image encoder and the decoder are nolboSingleObject_VAE's, and fit's span between
+    the head output and the decoder step (voxvae.train.Trainer.step_decoder) is a latent stage with ONE forward and ONE backward launch
+    (latent='hip') or the same algebra as torch autograd code (latent='torch'); its gradients continue through the 2D encoder and the prior
+    networks by torch autograd.  The training step is written once, here; a subclass names its prior networks (_priors, the structure
+    attribute being '_<structure key>_str') and the reference's constants, and supplies what differs:
+        _enc_layout() -> (width of the head output, its layout in words)
+        _prior_outputs(onehots) -> the prior networks in training mode on the step's one-hots: the tuple of their (mean, logVar) tensors
+        _decoder_input_draw(B, r) -> the step's draw of what the decoder sees: None = z, or a [B, L] selector between z and z_prior
+        _latent_stage(latent, e, pri, eps, eps_p, draw, onehots) -> (z_in [B, L], extra = the latent terms of the total loss, kl [B],
+            reg [B], bfloat16 twin of z_in or None) on either leg;    _debug_extra(draw) -> the class's own keys of the _debug capture"""
+    _reg_weight = 1.0        # the regulariser's weight in the total loss
+    _network_l2 = True       # whether the sub-models' l2 terms are part of the total loss
 
-    def saveModel(self, save_path):
-        self.saveEncoder(save_path=save_path)
-        self.saveDecoder(save_path=save_path)
-        self.savePriorCategory(save_path=save_path)
+    def __init__(self, nolbo_structure, backbone_style=None, encoder_backbone=None, learning_rate=1e-4):
+        for _, structure, _ in self._priors:
+            setattr(self, structure, nolbo_structure[structure[1:-4]])
+        self._debug = None         # set to a dict to capture the latent stage's inputs and gradients of the next fit (tests)
+        nolboSingleObject_VAE.__init__(self, nolbo_structure, backbone_style=backbone_style, encoder_backbone=encoder_backbone,
+                                       dropout=False, learning_rate=learning_rate)
 
-    def loadModel(self, load_path):
-        self.loadEncoder(load_path=load_path)
-        self.loadDecoder(load_path=load_path)
-        self.loadPriorCategory(load_path=load_path)
+    def _buildModel(self):
+        nolboSingleObject_VAE._buildModel(self)
+        # ==============set prior network, under the reference's names (nolbo.py:85-87)
+        for net, structure, _ in self._priors:
+            setattr(self, net, priornet.priornet(structure=getattr(self, structure), device=self._device))
+
+    def _debug_extra(self, draw):
+        return {}
+
+    def fit(self, inputs, *, latent='hip', _rand=None):
+        """(input_images, output_images, one one-hot list per prior network) -> (loss_kl, loss_shape, loss_reg, pr, rc);
+        total = mean KL(q || priors) + shape + _reg_weight mean reg (+ the l2 terms of every sub-model with _network_l2); Adam on the 2D
+        encoder, the prior networks (torch) and the decoder (HIP).  `_rand` (tests) = dict(eps, eps_prior [B, L]) and the class's draw."""
+        input_images, output_images, *onehots = inputs
+        if latent not in ('hip', 'torch'):
+            raise ValueError("latent must be 'hip' or 'torch', got %r" % (latent,))
+        if len(onehots) != len(self._priors):
+            raise ValueError('inputs must be (input_images, output_images) and %d one-hot list(s), got %d values' % (len(self._priors), len(inputs)))
+        y, onehots = self._dev(output_images), [self._dev(o).contiguous() for o in onehots]
+        trainer, opt = self._image_trainer()
+        opt.zero_grad(set_to_none=True)
+        pri = self._prior_outputs(onehots)                    # in front of the 2D encoder: their dropout draws first (nolbo.py:95-100)
+        enc_out = self._head_output_training(input_images)
+        self._check_width(enc_out, *self._enc_layout())
+        B = enc_out.shape[0]
+        r = _rand or {}
+        eps, eps_p = self._draw_eps(B, r.get('eps')).contiguous(), self._draw_eps(B, r.get('eps_prior')).contiguous()
+        draw = self._decoder_input_draw(B, r)
+        l2 = self._l2_terms() if self._network_l2 else []     # nolbo.py:142-144; the decoder's: step_decoder(l2=)
+        e = enc_out.detach().float().contiguous().requires_grad_(True)
+        with torch.enable_grad():
+            z_in, extra, kl, reg, twin = self._latent_stage(latent, e, pri, eps, eps_p, draw, onehots)
+        if self._debug is not None:
+            for t in pri:
+                if t.requires_grad:
+                    t.retain_grad()
+        _, m, dz = trainer.step_decoder(z_in.detach().contiguous(), y, z_act=twin, l2=ae3D.L2_REG if self._network_l2 else 0.0)
+        torch.autograd.backward([z_in, extra] + l2, [dz.contiguous(), torch.ones_like(extra)] + [torch.ones_like(t) for t in l2])
+        if enc_out.requires_grad:
+            enc_out.backward(e.grad)
+        opt.step()
+        if self._debug is not None:                           # a constant log-variance has no gradient: None
+            self._debug.update({'enc_out': e.detach(), 'pri': [t.detach() for t in pri], 'z_in': z_in.detach(), 'dz_in': dz, 'd_enc_out': e.grad,
+                                'd_pri': [t.grad if t.requires_grad else None for t in pri]}, **self._debug_extra(draw))
+        return DeviceArray(kl.detach().mean()), DeviceArray(m[0]), DeviceArray(reg.detach().mean()), DeviceArray(m[1]), DeviceArray(m[2])
 
 
-class nolboSingleObject(nolboSingleObject_VAE):
+@_prior_checkpoints
+class nolboSingleObject(_PriorImageModel):
     """The reference's multi-modal model, nolbo.py:49-324: an image encoder that emits a category latent and an instance latent
     ([mean_c | logVar_c | mean_i | logVar_i]), a learned prior network for each, and missing-modality correction of the category
     half against the category prior.  Structure keys as the reference's: encoder_backbone (z_category_dim, z_inst_dim), encoder_head,
     decoder, prior_class, prior_inst.  The image encoder and the decoder are nolboSingleObject_VAE's (either image engine, the HIP
-    decoder engine); everything between the head output and the decoder input is ONE vv_mm_latent_eval (csrc/mm_latent.hip).
+    decoder engine); everything between the head output and the decoder input is ONE vv_mm_latent_eval (csrc/mm_latent.hip, through
+    voxvae.mm_latent.eval).
 
-    In fit the same span is vv_mm_latent_train_fwd and vv_mm_latent_train_bwd around the decoder's step on the HIP trainer."""
-
-    def __init__(self, nolbo_structure, backbone_style=None, encoder_backbone=None, learning_rate=1e-4):
-        self._prior_class_str = nolbo_structure['prior_class']
-        self._prior_inst_str = nolbo_structure['prior_inst']
-        self._debug = None         # set to a dict to capture the latent stage's inputs and gradients of the next fit (tests)
-        nolboSingleObject_VAE.__init__(self, nolbo_structure, backbone_style=backbone_style, encoder_backbone=encoder_backbone,
-                                       dropout=False, learning_rate=learning_rate)
+    fit (nolbo.py:90-159): inputs = (input_images, output_images, category_list, inst_list); total = mean KL(q || priors) + shape +
+    mean reg + the l2 terms of all five sub-models.  Its latent stage is ONE vv_mm_latent_train_fwd and, with the decoder's
+    d shape / d z_in, ONE vv_mm_latent_train_bwd (voxvae.mm_latent.latent_stage); latent='torch' runs the same algebra as an autograd
+    closure.  `_rand` (tests) = dict(eps, eps_prior [B, Lc+Li], mix (bool), noise [B, Lc+Li])."""
+    _priors = (('_priornet_class', '_prior_class_str', 'Category'), ('_priornet_inst', '_prior_inst_str', 'Inst'))
 
     @property
     def _latent_dim(self):
         """The decoder's input: the concatenated latent (what getSampledShape and its kin sample)."""
         return self._enc_backbone_str['z_category_dim'] + self._enc_backbone_str['z_inst_dim']
-
-    def _buildModel(self):
-        nolboSingleObject_VAE._buildModel(self)
-        # ==============set prior network (nolbo.py:85-87)
-        self._priornet_class = priornet.priornet(structure=self._prior_class_str, device=self._device)
-        self._priornet_inst = priornet.priornet(structure=self._prior_inst_str, device=self._device)
 
     def _latent_torch(self, e, pri, eps, eps_p, noise, cat_oh):
         """fit's latent algebra (nolbo.py:101-140, function.py:40-98) as torch autograd code: what vv_mm_latent_train_fwd / _bwd compute,
@@ -801,89 +915,25 @@ class nolboSingleObject(nolboSingleObject_VAE):
         mean = torch.cat([e[:, :Lc], e[:, 2 * Lc:2 * Lc + Li]], dim=1)
         lv = torch.clamp(torch.cat([e[:, Lc:2 * Lc], e[:, 2 * Lc + Li:]], dim=1), -10.0, 10.0)
         mean_p, lv_p = torch.cat([mean_cp, mean_ip], dim=1), torch.cat([lv_cp, lv_ip], dim=1)
-        z = mean + torch.sqrt(torch.exp(lv)) * eps                                    # function.py:35-38
-        z_prior = mean_p + torch.sqrt(torch.exp(lv_p)) * eps_p
-        z_in = z if noise is None else torch.where(noise == 0, z, z_prior)            # :122-123
-        kl = (0.5 * (lv_p - lv) + (torch.exp(lv) + (mean - mean_p) ** 2) / (2.0 * torch.exp(lv_p)) - 0.5).sum(-1)
+        z_in, kl = _sample_kl_torch(mean, lv, mean_p, lv_p, eps, eps_p, None if noise is None else noise == 0)   # :122-123
+        return z_in, kl, _pair_reg_torch(mean_cp, lv_cp, 3.0 * Lc) + _pair_reg_torch(mean_ip, lv_ip, 3.0 * Li, cat_oh)
 
-        def reg(m, l, dist, cls=None):
-            d = (torch.abs(m[:, None, :] - m[None, :, :]) / torch.exp(0.5 * l)[:, None, :]).sum(-1) - dist
-            v = torch.where(d > 0, torch.zeros_like(d), d * d)
-            if cls is not None:                                                       # only pairs of one class count
-                v = v * (torch.abs(cls[:, None, :] - cls[None, :, :]).sum(-1) <= 0).to(v.dtype)
-            return v.sum(-1)
+    def _enc_layout(self):
+        return 2 * self._latent_dim, 'mean_c | logVar_c | mean_i | logVar_i'
 
-        return z_in, kl, reg(mean_cp, lv_cp, 3.0 * Lc) + reg(mean_ip, lv_ip, 3.0 * Li, cat_oh)
+    def _prior_outputs(self, onehots):                                                # :95-97
+        return self._priornet_class(onehots[0], training=True) + self._priornet_inst(torch.cat(onehots, dim=-1), training=True)
 
-    def fit(self, inputs, *, latent='hip', _rand=None):
-        """nolbo.py:90-159: (input_images, output_images, category_list, inst_list) -> (loss_kl, loss_shape, loss_reg, pr, rc);
-        total = mean KL(q || priors) + shape + mean reg + the l2 terms of all five sub-models.  The head output and the two prior
-        networks run in torch; between them and the decoder step (voxvae.train.Trainer.step_decoder) the latent stage is ONE
-        vv_mm_latent_train_fwd and, with the decoder's d shape / d z_in, ONE vv_mm_latent_train_bwd; its gradients continue through
-        the 2D encoder and the prior networks by torch autograd; Adam on all of them.  latent='torch' runs the same algebra as an
-        autograd closure.  `_rand` (tests) = dict(eps, eps_prior [B, Lc+Li], mix (bool), noise [B, Lc+Li])."""
-        from voxvae import train as _T
-        if latent not in ('hip', 'torch'):
-            raise ValueError("latent must be 'hip' or 'torch', got %r" % (latent,))
-        input_images, output_images, category_list, inst_list = inputs
-        Lc, Li = self._enc_backbone_str['z_category_dim'], self._enc_backbone_str['z_inst_dim']
-        y, cat_oh, inst_oh = self._dev(output_images), self._dev(category_list).contiguous(), self._dev(inst_list).contiguous()
-        if getattr(self, '_trainer_mm', None) is None:
-            self._trainer_mm = _T.Trainer(None, self._dec_eng, variational=False, learning_rate=self._learning_rate)
-            mods = [m for m in (self._encoder_backbone, self._encoder_head, self._priornet_class, self._priornet_inst)
-                    if isinstance(m, torch.nn.Module)]
-            self._opt_mm = torch.optim.Adam([p for m in mods for p in m.parameters()], lr=self._learning_rate, eps=1e-7)   # Keras epsilon
-        self._opt_mm.zero_grad(set_to_none=True)
-        pri = self._priornet_class(cat_oh, training=True) + self._priornet_inst(torch.cat([cat_oh, inst_oh], dim=-1), training=True)   # :95-97
-        enc_out = self._encoder_2d(input_images, training=True)                      # :100
-        if not (torch.is_tensor(enc_out) and enc_out.requires_grad):                  # a 2D encoder without parameters, or head outputs
-            enc_out = self._dev(enc_out)
-        B, C = enc_out.shape[0], cat_oh.shape[1]
-        if enc_out.dim() != 2 or enc_out.shape[1] != 2 * Lc + 2 * Li:
-            raise ValueError('the encoder must emit [B, %d] (mean_c | logVar_c | mean_i | logVar_i), got %s' % (2 * Lc + 2 * Li, tuple(enc_out.shape)))
-        r = _rand or {}
-        eps, eps_p = self._draw_eps(B, r.get('eps')).contiguous(), self._draw_eps(B, r.get('eps_prior')).contiguous()
-        mix = bool(r['mix']) if 'mix' in r else not (np.random.rand() > 0.5)          # :119: z itself with probability 1/2
-        noise = None
-        if mix:                                                                       # :122, the same RNG call
-            noise = self._dev(r['noise'] if 'noise' in r else
-                              np.random.choice(a=[False, True], size=(B, Lc + Li), p=[0.5, 0.5]).astype('float32')).contiguous()
-        l2 = [l for m in (self._encoder_head, self._encoder_backbone, self._priornet_class, self._priornet_inst) if hasattr(m, 'losses')
-              for l in m.losses]                                                      # :142-144; the decoder's: step_decoder(l2=)
-        l2 = [torch.stack(l2).sum()] if l2 else []
-        e = enc_out.detach().float().contiguous()
+    def _decoder_input_draw(self, B, r):
+        """:119-122: z itself with probability 1/2, else noise ~ Bernoulli(1/2) per element, 1 where z_prior stands in."""
+        return self._draw_mix(B, self._latent_dim, r, a=(False, True), missing_pr=0.5)
+
+    def _latent_stage(self, latent, e, pri, eps, eps_p, noise, onehots):
         if latent == 'torch':
-            e.requires_grad_(True)
-            with torch.enable_grad():
-                z_in, kl, reg = self._latent_torch(e, pri, eps, eps_p, noise, cat_oh)
-                extra = kl.mean() + reg.mean()
-            for t in pri:
-                if self._debug is not None and t.requires_grad:
-                    t.retain_grad()
-            _, m, dz = self._trainer_mm.step_decoder(z_in.detach().contiguous(), y, l2=ae3D.L2_REG)
-            torch.autograd.backward([z_in, extra] + l2, [dz, torch.ones_like(extra)] + [torch.ones_like(t) for t in l2])
-            d_e, d_pri = e.grad, [t.grad if self._debug is not None and t.requires_grad else None for t in pri]
-            if enc_out.requires_grad:
-                enc_out.backward(d_e)
-        else:
-            p = [t.detach().float().contiguous() for t in pri]
-            new = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=self._device)
-            z_in, kl, reg = new(B, Lc + Li), new(B), new(B)
-            z_act = new(B, Lc + Li, dt=torch.bfloat16) if self._act_dt != _L.VV_F32 else None
-            common = (_L.ptr(e), _L.ptr(eps), _L.ptr(p[0]), _L.ptr(p[1]), _L.ptr(p[2]), _L.ptr(p[3]), _L.ptr(eps_p), _L.ptr(noise), _L.ptr(cat_oh))
-            _L.call('vv_mm_latent_train_fwd', *common, _L.ptr(z_in), _L.ptr(z_act), self._act_dt, _L.ptr(kl), _L.ptr(reg), B, Lc, Li, C, _st())
-            _, m, dz = self._trainer_mm.step_decoder(z_in, y, z_act=z_act, l2=ae3D.L2_REG)
-            d_e = new(B, 2 * Lc + 2 * Li)
-            d_pri = [new(*t.shape) if t.requires_grad else None for t in pri]         # a constant log-variance has no gradient
-            _L.call('vv_mm_latent_train_bwd', *common, _L.ptr(dz.contiguous()), 1.0 / B, _L.ptr(d_e), *[_L.ptr(g) for g in d_pri],
-                    B, Lc, Li, C, _st())
-            heads = [(t, g) for t, g in zip(pri, d_pri) if g is not None] + ([(enc_out, d_e)] if enc_out.requires_grad else [])
-            torch.autograd.backward([t for t, _ in heads] + l2, [g for _, g in heads] + [torch.ones_like(t) for t in l2])
-        self._opt_mm.step()
-        if self._debug is not None:
-            self._debug.update({'enc_out': e.detach(), 'pri': [t.detach() for t in pri], 'z_in': z_in.detach(), 'dz_in': dz, 'd_enc_out': d_e,
-                                'd_pri': d_pri})
-        return DeviceArray(kl.detach().mean()), DeviceArray(m[0]), DeviceArray(reg.detach().mean()), DeviceArray(m[1]), DeviceArray(m[2])
+            z_in, kl, reg = self._latent_torch(e, pri, eps, eps_p, noise, onehots[0])
+            return z_in, kl.mean() + reg.mean(), kl, reg, None
+        from voxvae import mm_latent as _ML
+        return _ML.latent_stage(e, *pri, eps, eps_p, noise, onehots[0], bf16=self._act_dt != _L.VV_F32)
 
     def _prior_means(self, category_list, category_indices, inst_indices, training):
         """prior_cat [C, Lc] and the instance prior's means of each sample [B, I, Li] (nolbo.py:166-181)."""
@@ -900,13 +950,13 @@ class nolboSingleObject(nolboSingleObject_VAE):
         """reference nolbo.py:161-259 -> (pred, loss_shape, pr, rc, acc_cat, acc_inst) at missing_prob == 0, else these and
         (pred_corrected, loss_shape_corrected, pr_corrected, rc_corrected, acc_cat_corrected).  `_eps` [B, Lc+Li] (the category
         draw, then the instance draw), `_mask` [B, Lc] and `_eps2` [B, Lc] inject the draws."""
+        from voxvae import mm_latent as _ML
         input_images, output_images, category_list, inst_list = inputs
-        Lc, Li = self._enc_backbone_str['z_category_dim'], self._enc_backbone_str['z_inst_dim']
+        Lc = self._enc_backbone_str['z_category_dim']
         prior_cat, prior_inst = self._prior_means(category_list, category_indices, inst_indices, training)
         enc_out = self._enc_out(input_images, training=training)
-        B, C, I = enc_out.shape[0], prior_cat.shape[0], prior_inst.shape[1]
-        if enc_out.dim() != 2 or enc_out.shape[1] != 2 * Lc + 2 * Li:
-            raise ValueError('the encoder must emit [B, %d] (mean_c | logVar_c | mean_i | logVar_i), got %s' % (2 * Lc + 2 * Li, tuple(enc_out.shape)))
+        self._check_width(enc_out, *self._enc_layout())
+        B = enc_out.shape[0]
         y, cat_oh, inst_oh = self._dev(output_images), self._dev(category_list).contiguous(), self._dev(inst_list).contiguous()
         eps = self._draw_eps(B, _eps).contiguous()
         mask = eps2 = None
@@ -914,15 +964,8 @@ class nolboSingleObject(nolboSingleObject_VAE):
             mask = self._draw_mask(B, missing_prob, _mask, Lc).contiguous()             # :202-203, the same RNG call
             eps2 = (torch.randn(B, Lc, dtype=torch.float32, device=self._device) if _eps2 is None else self._dev(_eps2)).contiguous()
         act_dt = _L.VV_F32 if training else self._act_dt                               # training: float32 to the decoder entry (_eval_hooks)
-        new = lambda dt=torch.float32: torch.empty(B, Lc + Li, dtype=dt, device=self._device)
-        z, zc = new(), (new() if mask is not None else None)
-        twin = act_dt != _L.VV_F32
-        z_act, zc_act = (new(torch.bfloat16) if twin else None), (new(torch.bfloat16) if twin and mask is not None else None)
-        idx = torch.empty(B, 4, dtype=torch.int32, device=self._device)
-        acc = torch.empty(3, dtype=torch.float32, device=self._device)
-        _L.call('vv_mm_latent_eval', _L.ptr(enc_out), _L.ptr(eps), _L.ptr(mask), _L.ptr(eps2), _L.ptr(prior_cat), _L.ptr(prior_inst),
-                _L.ptr(cat_oh), _L.ptr(inst_oh), _L.ptr(z), _L.ptr(zc), _L.ptr(z_act), _L.ptr(zc_act), act_dt, _L.ptr(idx), _L.ptr(acc),
-                B, Lc, Li, C, I, _st())
+        z, zc, z_act, zc_act, idx, acc = _ML.eval(enc_out, eps, mask, eps2, prior_cat, prior_inst, cat_oh, inst_oh, act_dt)
+        twin = z_act is not None
         decode = self._eval_hooks(training)[1]
         pred, _, m = decode(z_act if twin else z, y, None)                             # :229-235
         self._z, self._nearest = DeviceArray(z), DeviceArray(idx)
@@ -932,30 +975,6 @@ class nolboSingleObject(nolboSingleObject_VAE):
         pred_c, _, mc = decode(zc_act if twin else zc, y, None)                        # :252-258
         self._z_corrected = DeviceArray(zc)
         return res + self._scored(pred_c, mc) + (DeviceArray(acc[2]),)
-
-    def savePriorCategory(self, save_path):
-        self._priornet_class.save_weights(os.path.join(save_path, self._prior_class_str['name']))
-
-    def savePriorInst(self, save_path):
-        self._priornet_inst.save_weights(os.path.join(save_path, self._prior_inst_str['name']))
-
-    def saveModel(self, save_path):
-        self.saveEncoder(save_path)
-        self.saveDecoder(save_path)
-        self.savePriorCategory(save_path)
-        self.savePriorInst(save_path)
-
-    def loadPriorCategory(self, load_path, file_name=None):
-        self._priornet_class.load_weights(os.path.join(load_path, self._prior_class_str['name'] if file_name is None else file_name))
-
-    def loadPriorInst(self, load_path, file_name=None):
-        self._priornet_inst.load_weights(os.path.join(load_path, self._prior_inst_str['name'] if file_name is None else file_name))
-
-    def loadModel(self, load_path):
-        self.loadEncoder(load_path)
-        self.loadDecoder(load_path)
-        self.loadPriorCategory(load_path)
-        self.loadPriorInst(load_path)
 
 
 class nolboSingleObject_AE(nolboSingleObject_VAE):
@@ -974,156 +993,72 @@ class nolboSingleObject_AE(nolboSingleObject_VAE):
         """nolbo.py:580-610: (input_images, output_images) -> (loss_shape, pr, rc); total = shape + the l2 terms of head, backbone
         and decoder.  dropout=True: inverted dropout on z at a rate ~ U[0,1) per step (:586-588); `_dropout` = (rate, keep [B, L])
         injects it."""
-        from voxvae import train as _T
         input_images, output_images = inputs
         y = self._dev(output_images)
-        if self._trainer2d is None:
-            self._trainer2d = _T.Trainer(None, self._dec_eng, variational=False, learning_rate=self._learning_rate)
-            mods = [m for m in (self._encoder_backbone, self._encoder_head) if isinstance(m, torch.nn.Module)]
-            params = [p for m in mods for p in m.parameters()]
-            self._opt2d = torch.optim.Adam(params, lr=self._learning_rate, eps=1e-7) if params else None   # Keras epsilon
-        z = self._encoder_2d(input_images, training=True)
-        if not (torch.is_tensor(z) and z.requires_grad):
-            z = self._dev(z)
+        trainer, opt = self._image_trainer()
+        z = self._head_output_training(input_images)
         z_in, keep = z.detach().float().contiguous(), None
         if self._dropout:
-            rate, keep = _dropout if _dropout is not None else (float(np.random.rand()), None)
-            keep = self._draw_keep(z_in.shape[0], z_in.shape[1], rate) if keep is None else self._dev(keep)
-            keep = (torch.rand(z_in.shape, device=self._device) >= rate).float() if keep is None else keep
-            keep = keep * (1.0 / (1.0 - rate))
+            keep, scale = self._draw_dropout(z_in.shape[0], z_in.shape[1], *(_dropout or ()))
+            keep = keep * scale
             z_in = z_in * keep
-        _, m, dz = self._trainer2d.step_decoder(z_in, y, l2=ae3D.L2_REG)               # + decoder.losses, :595-596
-        if self._opt2d is not None and z.requires_grad:
-            self._opt2d.zero_grad(set_to_none=True)
-            reg = [l for mod in (self._encoder_head, self._encoder_backbone) if hasattr(mod, 'losses') for l in mod.losses]
-            reg = [torch.stack(reg).sum()] if reg else []
+        _, m, dz = trainer.step_decoder(z_in, y, l2=ae3D.L2_REG)                       # + decoder.losses, :595-596
+        if opt is not None and z.requires_grad:
+            opt.zero_grad(set_to_none=True)
+            reg = self._l2_terms()
             torch.autograd.backward([z] + reg, [dz if keep is None else dz * keep] + [torch.ones_like(t) for t in reg])
-            self._opt2d.step()
+            opt.step()
         return DeviceArray(m[0]), DeviceArray(m[1]), DeviceArray(m[2])
 
 
-class _OnePriorImageModel(nolboSingleObject_VAE):
+class _OnePriorImageModel(_PriorImageModel):
     """What nolboSingleObject_instOnly and nolboSingleObject_category_only share: an image encoder that emits ONE latent group
-    ([mean | logVar]), ONE learned prior network over the sample's one-hot, and a fit whose span between the head output and the decoder
-    step (voxvae.train.Trainer.step_decoder) is ONE vv_prior_latent_train_fwd and, with the decoder's d shape / d z_in, ONE
-    vv_prior_latent_train_bwd (csrc/prior_latent.hip, through voxvae.prior_latent.latent_stage); the gradients continue through the 2D
-    encoder and the prior network by torch autograd.  The image encoder and the decoder are nolboSingleObject_VAE's.  A subclass names
-    its structure keys and the reference's constants."""
+    ([mean | logVar]), ONE learned prior network over the sample's one-hot, and as latent stage ONE vv_prior_latent_train_fwd and ONE
+    vv_prior_latent_train_bwd (csrc/prior_latent.hip, through voxvae.prior_latent.latent_stage).  A subclass names its structure keys and
+    the reference's constants."""
     _z_key = None            # the latent's width in nolbo_structure['encoder_backbone']
-    _prior_key = None        # the prior network's structure in nolbo_structure
-    _prior_attr = None       # the attribute that holds the prior network
     _dist_per_dim = None     # dist_in_z_space = _dist_per_dim * L
-    _reg_weight = None       # the regulariser's weight in the total loss
-    _network_l2 = None       # whether the sub-models' l2 terms are part of the total loss
-
-    def __init__(self, nolbo_structure, backbone_style=None, encoder_backbone=None, learning_rate=1e-4):
-        self._prior_str = nolbo_structure[self._prior_key]
-        setattr(self, '_%s_str' % self._prior_key, self._prior_str)        # the reference's name: _prior_inst_str / _prior_class_str
-        self._debug = None         # set to a dict to capture the latent stage's inputs and gradients of the next fit (tests)
-        nolboSingleObject_VAE.__init__(self, nolbo_structure, backbone_style=backbone_style, encoder_backbone=encoder_backbone,
-                                       dropout=False, learning_rate=learning_rate)
 
     @property
     def _latent_dim(self):
         return self._enc_backbone_str[self._z_key]
 
-    def _buildModel(self):
-        nolboSingleObject_VAE._buildModel(self)
-        # ==============set prior network, under the reference's name (_priornet_inst / _priornet_class)
-        setattr(self, self._prior_attr, priornet.priornet(structure=self._prior_str, device=self._device))
-
     @property
     def _priornet(self):
-        return getattr(self, self._prior_attr)
+        return getattr(self, self._priors[0][0])
 
-    def _latent_torch(self, e, pri, eps, eps_p, keep, dist):
-        """fit's latent algebra (function.py:35-38, 40-71, 84-98) as torch autograd code: what vv_prior_latent_train_fwd / _bwd compute,
-        kept as the comparison leg (latent='torch').  -> z_in [B, L], kl [B], reg [B]."""
-        Lz = self._latent_dim
-        mean_p, lv_p = pri
-        mean, lv = e[:, :Lz], torch.clamp(e[:, Lz:], -10.0, 10.0)
-        z = mean + torch.sqrt(torch.exp(lv)) * eps
-        z_prior = mean_p + torch.sqrt(torch.exp(lv_p)) * eps_p
-        z_in = z if keep is None else torch.where(keep == 1., z, z_prior)
-        kl = (0.5 * (lv_p - lv) + (torch.exp(lv) + (mean - mean_p) ** 2) / (2.0 * torch.exp(lv_p)) - 0.5).sum(-1)
-        d = (torch.abs(mean_p[:, None, :] - mean_p[None, :, :]) / torch.exp(0.5 * lv_p)[:, None, :]).sum(-1) - dist
-        return z_in, kl, torch.where(d > 0, torch.zeros_like(d), d * d).sum(-1)
+    def _enc_layout(self):
+        return 2 * self._latent_dim, 'mean | logVar'
 
-    def _decoder_input_keep(self, B, Lz, r):
-        """The step's draw of what the decoder sees: None = z; else keep [B, L], 1 where the element is z's, 0 where z_prior's."""
-        raise NotImplementedError
+    def _prior_outputs(self, onehots):
+        return self._priornet(onehots[0], training=True)
 
-    def fit(self, inputs, *, latent='hip', _rand=None):
+    def _latent_stage(self, latent, e, pri, eps, eps_p, keep, onehots):
+        dist = float(self._dist_per_dim) * self._latent_dim
+        if latent == 'torch':
+            z_in, kl, reg = _one_prior_latent_torch(e, pri, eps, eps_p, keep, dist)
+            return z_in, kl.mean() + self._reg_weight * reg.mean(), kl, reg, None
         from voxvae import prior_latent as _PL
-        from voxvae import train as _T
-        if latent not in ('hip', 'torch'):
-            raise ValueError("latent must be 'hip' or 'torch', got %r" % (latent,))
-        input_images, output_images, onehot = inputs
-        Lz = self._latent_dim
-        y, onehot = self._dev(output_images), self._dev(onehot).contiguous()
-        if getattr(self, '_trainer_p', None) is None:
-            self._trainer_p = _T.Trainer(None, self._dec_eng, variational=False, learning_rate=self._learning_rate)
-            mods = [m for m in (self._encoder_backbone, self._encoder_head, self._priornet) if isinstance(m, torch.nn.Module)]
-            self._opt_p = torch.optim.Adam([p for m in mods for p in m.parameters()], lr=self._learning_rate, eps=1e-7)   # Keras epsilon
-        self._opt_p.zero_grad(set_to_none=True)
-        pri = self._priornet(onehot, training=True)
-        enc_out = self._encoder_2d(input_images, training=True)
-        if not (torch.is_tensor(enc_out) and enc_out.requires_grad):                  # a 2D encoder without parameters, or head outputs
-            enc_out = self._dev(enc_out)
-        B = enc_out.shape[0]
-        if enc_out.dim() != 2 or enc_out.shape[1] != 2 * Lz:
-            raise ValueError('the encoder must emit [B, %d] (mean | logVar), got %s' % (2 * Lz, tuple(enc_out.shape)))
-        r = _rand or {}
-        eps, eps_p = self._draw_eps(B, r.get('eps')).contiguous(), self._draw_eps(B, r.get('eps_prior')).contiguous()
-        keep = self._decoder_input_keep(B, Lz, r)
-        dist = float(self._dist_per_dim) * Lz
-        l2 = []
-        if self._network_l2:
-            l2 = [l for m in (self._encoder_head, self._encoder_backbone, self._priornet) if hasattr(m, 'losses') for l in m.losses]
-            l2 = [torch.stack(l2).sum()] if l2 else []                               # the decoder's: step_decoder(l2=)
-        e = enc_out.detach().float().contiguous().requires_grad_(True)
-        twin = None
-        with torch.enable_grad():
-            if latent == 'torch':
-                z_in, kl, reg = self._latent_torch(e, pri, eps, eps_p, keep, dist)
-                extra = kl.mean() + self._reg_weight * reg.mean()
-            else:
-                z_in, extra, kl, reg, twin = _PL.latent_stage(e, pri[0], pri[1], eps, eps_p, keep, dist, self._reg_weight,
-                                                              bf16=self._act_dt != _L.VV_F32)
-        if self._debug is not None:
-            for t in pri:
-                if t.requires_grad:
-                    t.retain_grad()
-        _, m, dz = self._trainer_p.step_decoder(z_in.detach().contiguous(), y, z_act=twin, l2=ae3D.L2_REG if self._network_l2 else 0.0)
-        torch.autograd.backward([z_in, extra] + l2, [dz.contiguous(), torch.ones_like(extra)] + [torch.ones_like(t) for t in l2])
-        if enc_out.requires_grad:
-            enc_out.backward(e.grad)
-        self._opt_p.step()
-        if self._debug is not None:
-            self._debug.update({'enc_out': e.detach(), 'pri': [t.detach() for t in pri], 'keep': keep, 'z_in': z_in.detach(), 'dz_in': dz,
-                                'd_enc_out': e.grad, 'd_pri': [t.grad if t.requires_grad else None for t in pri], 'dist': dist,
-                                'reg_weight': self._reg_weight})
-        return DeviceArray(kl.detach().mean()), DeviceArray(m[0]), DeviceArray(reg.detach().mean()), DeviceArray(m[1]), DeviceArray(m[2])
+        return _PL.latent_stage(e, pri[0], pri[1], eps, eps_p, keep, dist, self._reg_weight, bf16=self._act_dt != _L.VV_F32)
+
+    def _debug_extra(self, keep):
+        return {'keep': keep, 'dist': float(self._dist_per_dim) * self._latent_dim, 'reg_weight': self._reg_weight}
 
 
+@_prior_checkpoints
 class nolboSingleObject_instOnly(_OnePriorImageModel):
     """The reference's instance-only image model, nolbo.py:326-540 (train_kitti.py): one instance latent, a learned prior network over
     the instance one-hot.  Structure keys as the reference's: encoder_backbone (z_inst_dim), encoder_head, decoder, prior_inst.
-    fit (:365-415): total = mean KL(q || prior) + shape + mean reg (dist 10 L) + the l2 terms of all four sub-models; the decoder sees z
-    or, with probability 1/2, z_prior for the whole batch.  getEval (:417-485): ONE vv_inst_latent_eval between the head output and the
-    two decoder passes."""
-    _z_key, _prior_key, _prior_attr = 'z_inst_dim', 'prior_inst', '_priornet_inst'
+    fit (:365-415): inputs = (input_images, output_images, inst_list); total = mean KL(q || prior) + shape + mean reg (dist 10 L) + the
+    l2 terms of all four sub-models; the decoder sees z or, with probability 1/2 (`_rand['from_prior']`), z_prior for the whole batch.
+    getEval (:417-485): ONE vv_inst_latent_eval between the head output and the two decoder passes."""
+    _z_key, _priors = 'z_inst_dim', (('_priornet_inst', '_prior_inst_str', 'Inst'),)
     _dist_per_dim, _reg_weight, _network_l2 = 10.0, 1.0, True
 
-    def _decoder_input_keep(self, B, Lz, r):
-        """:383-386: `rand < 0.5` -> decoder(z), else decoder(z_prior); `_rand['from_prior']` (bool) injects the choice."""
+    def _decoder_input_draw(self, B, r):
+        """:383-386: `rand < 0.5` -> decoder(z), else decoder(z_prior): an all-zero keep; `_rand['from_prior']` (bool) injects the choice."""
         from_prior = bool(r['from_prior']) if 'from_prior' in r else not (np.random.rand() < 0.5)
-        return torch.zeros(B, Lz, dtype=torch.float32, device=self._device) if from_prior else None
-
-    def fit(self, inputs, *, latent='hip', _rand=None):
-        """nolbo.py:365-415: (input_images, output_images, inst_list) -> (loss_kl, loss_shape, loss_reg, pr, rc).  latent='torch' runs
-        the same algebra as an autograd closure.  `_rand` (tests) = dict(eps, eps_prior [B, L], from_prior (bool))."""
-        return _OnePriorImageModel.fit(self, inputs, latent=latent, _rand=_rand)
+        return torch.zeros(B, self._latent_dim, dtype=torch.float32, device=self._device) if from_prior else None
 
     def getEval(self, input_images, output_images, inst_list=np.identity(10), missing_prob=0.1, training=True, *, _eps=None, _mask=None,
                 _fill=None):
@@ -1137,8 +1072,7 @@ class nolboSingleObject_instOnly(_OnePriorImageModel):
         with torch.no_grad():
             enc_out = self._enc_out(input_images, training=training).detach()
         B, Lz = enc_out.shape[0], self._latent_dim
-        if enc_out.dim() != 2 or enc_out.shape[1] != 2 * Lz:
-            raise ValueError('the encoder must emit [B, %d] (mean | logVar), got %s' % (2 * Lz, tuple(enc_out.shape)))
+        self._check_width(enc_out, *self._enc_layout())
         y = self._dev(output_images)
         eps = self._draw_eps(B, _eps).contiguous()
         mask = fill = None
@@ -1153,65 +1087,23 @@ class nolboSingleObject_instOnly(_OnePriorImageModel):
         self._z, self._z_corrected, self._nearest = DeviceArray(z), DeviceArray(zc), DeviceArray(idx)
         return self._scored(pred, m) + self._scored(pred_c, mc)
 
-    def savePriorInst(self, save_path):
-        self._priornet.save_weights(os.path.join(save_path, self._prior_str['name']))
 
-    def loadPriorInst(self, load_path, file_name=None):
-        self._priornet.load_weights(os.path.join(load_path, self._prior_str['name'] if file_name is None else file_name))
-
-    def saveModel(self, save_path):
-        self.saveEncoder(save_path)
-        self.saveDecoder(save_path)
-        self.savePriorInst(save_path)
-
-    def loadModel(self, load_path):
-        self.loadEncoder(load_path)
-        self.loadDecoder(load_path)
-        self.loadPriorInst(load_path)
-
-
+@_prior_checkpoints
 class nolboSingleObject_category_only(_OnePriorImageModel):
     """The reference's category-only image model, nolbo.py:984-1204 (train_pascal_category.py, test_pascal_category.py): one category
     latent, a learned prior network over the category one-hot.  Structure keys as the reference's: encoder_backbone (z_category_dim),
-    encoder_head, decoder, prior_class.  fit (:1023-1075): total = mean KL(q || prior) + shape + 0.01 mean reg (dist 3 L), no network l2
-    terms; the decoder sees z or, with probability 1/2, z with 30 % of its elements replaced by z_prior's.  getEval (:1077-1149) is
+    encoder_head, decoder, prior_class.  fit (:1023-1075): inputs = (input_images, output_images, category_list); total = mean KL(q ||
+    prior) + shape + 0.01 mean reg (dist 3 L), no network l2 terms; the decoder sees z or, with probability 1/2 (`_rand['mix']`), z with
+    30 % of its elements (`_rand['noise']` [B, L], 0 there) replaced by z_prior's.  getEval (:1077-1149) is
     nolboSingleObject_VAE's with the prototype table replaced by the prior network's means over `category_indices`."""
-    _z_key, _prior_key, _prior_attr = 'z_category_dim', 'prior_class', '_priornet_class'
+    _z_key, _priors = 'z_category_dim', (('_priornet_class', '_prior_class_str', 'Category'),)
     _dist_per_dim, _reg_weight, _network_l2 = 3.0, 0.01, False
 
-    def _decoder_input_keep(self, B, Lz, r):
-        """:1042-1047: `rand > 0.5` -> decoder(z), else keep ~ Bernoulli(0.7) per element (the same RNG call); `_rand['mix']` (bool) and
-        `_rand['noise']` [B, L] inject them."""
-        mix = bool(r['mix']) if 'mix' in r else not (np.random.rand() > 0.5)
-        if not mix:
-            return None
-        missing_pr = 0.3
-        return self._dev(r['noise'] if 'noise' in r else
-                         np.random.choice(a=[True, False], size=(B, Lz), p=[1. - missing_pr, missing_pr]).astype('float32')).contiguous()
-
-    def fit(self, inputs, *, latent='hip', _rand=None):
-        """nolbo.py:1023-1075: (input_images, output_images, category_list) -> (loss_kl, loss_shape, loss_reg, pr, rc).  latent='torch'
-        runs the same algebra as an autograd closure.  `_rand` (tests) = dict(eps, eps_prior [B, L], mix (bool), noise [B, L])."""
-        return _OnePriorImageModel.fit(self, inputs, latent=latent, _rand=_rand)
+    def _decoder_input_draw(self, B, r):
+        return self._draw_mix(B, self._latent_dim, r)                                  # :1042-1047
 
     def getEval(self, inputs, category_indices=np.identity(12), training=False, missing_prob=0.0, *, _eps=None, _mask=None, _eps2=None):
         """nolbo.py:1077-1149 -> the 10-tuple of the VAE class, classified / corrected against the prior means."""
         mean_prior, _ = self._priornet(np.asarray(category_indices, dtype='float32'), training=bool(training))
         return _ModelnetBase.getEval(self, inputs, category_vectors=mean_prior.detach().contiguous(), training=training,
                                      missing_prob=missing_prob, _eps=_eps, _mask=_mask, _eps2=_eps2)
-
-    def savePriorCategory(self, save_path):
-        self._priornet.save_weights(os.path.join(save_path, self._prior_str['name']))
-
-    def loadPriorCategory(self, load_path, file_name=None):
-        self._priornet.load_weights(os.path.join(load_path, self._prior_str['name'] if file_name is None else file_name))
-
-    def saveModel(self, save_path):
-        self.saveEncoder(save_path)
-        self.saveDecoder(save_path)
-        self.savePriorCategory(save_path)
-
-    def loadModel(self, load_path):
-        self.loadEncoder(load_path)
-        self.loadDecoder(load_path)
-        self.loadPriorCategory(load_path)

@@ -83,10 +83,9 @@ class _LatentStage(torch.autograd.Function):
         ctx.saved = (e, m, lv, eps, eps_p, keep)
         ctx.consts = (float(dist), float(reg_weight))
         extra = kl.mean() + float(reg_weight) * reg.mean()
-        ctx.mark_non_differentiable(kl, reg)
         if twin is None:
             twin = z_in.new_empty(0)
-        ctx.mark_non_differentiable(twin)
+        ctx.mark_non_differentiable(kl, reg, twin)            # one call: a second one would replace the first one's set
         return z_in, extra, kl, reg, twin
 
     @staticmethod

@@ -184,7 +184,7 @@ def test_fit_hip_against_torch(mix, dtype):
         out = [float(v) for v in m.fit(inputs, latent=latent, _rand=rand)]
         grads = {n: p.grad.detach().cpu().numpy() for mod, tag in ((m._encoder_backbone, 'enc'), (m._priornet_class, 'pc'), (m._priornet_inst, 'pi'))
                  for n, p in ((tag + '/' + n, p) for n, p in mod.named_parameters())}
-        g_dec = {k: m._trainer_mm._g('dec/' + k).detach().cpu().numpy().copy() for k in w0 if not k.endswith(('moving_mean', 'moving_variance'))}
+        g_dec = {k: m._trainer2d._g('dec/' + k).detach().cpu().numpy().copy() for k in w0 if not k.endswith(('moving_mean', 'moving_variance'))}
         legs[latent] = dict(out=out, cap=m._debug, grads=grads, g_dec=g_dec, w={k: v.detach().cpu().numpy() for k, v in m._dec_eng.params.items()},
                             w0={k: v.cpu().numpy() for k, v in w0.items()})
     h, t = legs['hip'], legs['torch']
