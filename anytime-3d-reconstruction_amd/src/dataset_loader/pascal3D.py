@@ -71,3 +71,145 @@ class dataLoaderSingleObject(object):
         inst = np.zeros((len(idx), 1), dtype='float32') if self._insts is None else np.eye(int(self._instances), dtype='float32')[self._insts[idx]]
         e = self._euler[idx]
         return inst, cls, np.sin(e), np.cos(e), imgs.astype('float32'), out.astype('float32')
+
+
+class deviceDataLoaderSingleObject(object):
+    """On-device variant of dataLoaderSingleObject: the photos live in device memory as one uint8 arena, the CAD grids as packed bits, and
+    getNextBatch builds the batch with the reference's own input chain (pascal3D.py:216-283: crop with a random border, flip, colour
+    perturbation, warpAffine, cubic resize, / 255) in launches -- permutation slice, vv_augment_draw, vv_augment_images, the existing
+    vv_unpack_bits_gather -- with no host round trip.  Same constructor strings (None, 'synthetic:N:D[:I]'), same six return values in the
+    same order, as float32 device tensors.  The azimuth's sign follows the horizontal flip (:247-248).
+
+    The synthetic stand-in serves seeded "photos": uint8 images of differing sizes, one per object, with a box; the object's three
+    max-projections are pasted at the box over a seeded textured background, so crop, border and warp all matter.  `from_arrays` takes
+    decoded data instead.  The draws are a pure function of (voxvae.manual_seed's seed, rank, step): voxvae/augment.py; `last_params` holds
+    the rows of the last batch.  GaussianBlur and AddToHueAndSaturation are drawn and not applied (csrc/augment.h)."""
+
+    def __init__(self, trainOrVal='train', Pascal3DDataPath=None, voxel=64, instances=None, device=None, seed=None):
+        n = 256 if trainOrVal == 'train' else 96
+        if isinstance(Pascal3DDataPath, str) and Pascal3DDataPath.startswith('synthetic:'):
+            parts = Pascal3DDataPath.split(':')
+            n = int(parts[1])
+            voxel = int(parts[2]) if len(parts) > 2 else voxel
+            instances = int(parts[3]) if len(parts) > 3 else instances
+        elif Pascal3DDataPath is not None:
+            raise FileNotFoundError('Pascal3D+ is not available in this build; pass None or synthetic:N:D[:I]')
+        data_seed = 4321 if trainOrVal == 'train' else 8765
+        rng = np.random.default_rng(data_seed)
+        voxels = syn.make_voxels(n, voxel, seed=data_seed)[..., 0]           # [n,D,D,D] in {0,1}
+        classes = rng.integers(0, CLASSES, n)
+        euler = rng.uniform(-np.pi, np.pi, (n, 3)).astype('float32')
+        insts = None if instances is None else np.random.default_rng(data_seed + 1).integers(0, int(instances), n)
+        images, boxes = self._photos(voxels, np.random.default_rng(data_seed + 2))
+        self._setup(images, boxes, classes, np.arange(n), euler, voxels, insts, instances, None, device,
+                    data_seed if seed is None else seed, trainOrVal == 'train')
+
+    @classmethod
+    def from_arrays(cls, images, boxes, classes, cad_index, euler, cad_grids, inst_index=None, instances=None, image_index=None, device=None,
+                    seed=None, shuffle=True):
+        """images: uint8 [rows, cols, 3] arrays; boxes [n, 4] = (colMin, rowMin, colMax, rowMax) in pixels; classes [n] in 0 .. 11;
+        cad_index [n] rows of cad_grids [m, D, D, D] (occupancy, binarised at 0.5); euler [n, 3] = (azimuth, elevation, in-plane
+        rotation) in radians.  image_index [n] (default: object i is in image i) lets several objects share a photo; instances with
+        inst_index (default cad_index) makes instList the one-hot [n, instances], otherwise it is the [n, 1] zeros."""
+        self = cls.__new__(cls)
+        insts = None if instances is None else np.asarray(cad_index if inst_index is None else inst_index)
+        self._setup(images, boxes, classes, cad_index, euler, cad_grids, insts, instances, image_index, device, seed, shuffle)
+        return self
+
+    @staticmethod
+    def _photos(voxels, rng):
+        n, D = voxels.shape[:2]
+        images, boxes = [], np.empty((n, 4), dtype='float32')
+        for i in range(n):
+            rows, cols = int(rng.integers(2 * D, 4 * D)), int(rng.integers(2 * D, 4 * D))
+            coarse = rng.integers(0, 256, (rows // 8 + 1, cols // 8 + 1, 3))
+            photo = np.repeat(np.repeat(coarse, 8, axis=0), 8, axis=1)[:rows, :cols] // 2 + rng.integers(0, 64, (rows, cols, 3))
+            bh, bw = int(rng.integers(rows // 3, (2 * rows) // 3)), int(rng.integers(cols // 3, (2 * cols) // 3))
+            r0, c0 = int(rng.integers(0, rows - bh)), int(rng.integers(0, cols - bw))
+            proj = np.stack([voxels[i].max(axis=ax) for ax in range(3)], axis=-1)          # [D,D,3]
+            ri, ci = np.arange(bh) * D // bh, np.arange(bw) * D // bw
+            obj = proj[ri][:, ci]
+            region = photo[r0:r0 + bh, c0:c0 + bw]
+            region[obj.max(axis=-1) > 0] = (obj * 255)[obj.max(axis=-1) > 0]
+            images.append(photo.astype('uint8'))
+            f = rng.uniform(0, 1, 4)                                                        # boxes are not on the pixel grid
+            boxes[i] = (c0 + f[0], r0 + f[1], c0 + bw - f[2], r0 + bh - f[3])
+        return images, boxes
+
+    def _setup(self, images, boxes, classes, cad_index, euler, cad_grids, insts, instances, image_index, device, seed, shuffle):
+        import torch
+        import voxvae
+        from voxvae import augment as _A
+        from voxvae import lib as _L
+        self._torch, self._A, self._L = torch, _A, _L
+        self._device = torch.device(device or voxvae.default_device())
+        boxes = np.ascontiguousarray(boxes, dtype='float32').reshape(-1, 4)
+        n = boxes.shape[0]
+        image_index = np.arange(n) if image_index is None else np.asarray(image_index)
+        classes, cad_index, euler = np.asarray(classes), np.asarray(cad_index), np.asarray(euler, dtype='float32').reshape(-1, 3)
+        grids = np.asarray(cad_grids)
+        grids = grids[..., 0] if grids.ndim == 5 else grids
+        if not (len(image_index) == len(classes) == len(cad_index) == len(euler) == n):
+            raise ValueError('boxes, classes, cad_index, euler and image_index must name the same %d objects' % n)
+        if image_index.min() < 0 or image_index.max() >= len(images) or cad_index.min() < 0 or cad_index.max() >= grids.shape[0]:
+            raise ValueError('image_index / cad_index outside the images / CAD grids')
+        if not np.isfinite(boxes).all():
+            raise ValueError('boxes must be finite')
+        # every box at least 2 px in both extents after the reference's truncation at border ratio 0
+        ext = np.array([images[i].shape[:2] for i in image_index], dtype='float32')
+        c0, c1 = np.maximum(0, boxes[:, 0]).astype(int), np.minimum(ext[:, 1], boxes[:, 2]).astype(int)
+        r0, r1 = np.maximum(0, boxes[:, 1]).astype(int), np.minimum(ext[:, 0], boxes[:, 3]).astype(int)
+        bad = np.flatnonzero(~((c1 - c0 >= 2) & (r1 - r0 >= 2)))
+        if bad.size:
+            raise ValueError('boxes under 2 px after truncation to the image: objects %s' % bad[:8].tolist())
+        self._sample_shape = tuple(grids.shape[1:]) + (1,)
+        self._voxels = int(np.prod(self._sample_shape))
+        if self._voxels % 8:
+            raise ValueError('voxel count per CAD grid must be a multiple of 8')
+        dev = self._device
+        self._arena = _A.ImageArena.from_arrays(images, device=dev)
+        self._packed = torch.from_numpy(np.ascontiguousarray(np.packbits(grids.reshape(grids.shape[0], -1) > 0.5, axis=1, bitorder='little'))).to(dev)
+        self._image_index = torch.from_numpy(image_index.astype('int32')).to(dev)
+        self._cad_index = torch.from_numpy(cad_index.astype('int32')).to(dev)
+        self._boxes = torch.from_numpy(boxes).to(dev)
+        self._cls = torch.from_numpy(np.eye(CLASSES, dtype='float32')[classes]).to(dev)
+        self._inst = torch.from_numpy(np.zeros((n, 1), dtype='float32') if insts is None else np.eye(int(instances), dtype='float32')[insts]).to(dev)
+        self._sin, self._cos = torch.from_numpy(np.sin(euler)).to(dev), torch.from_numpy(np.cos(euler)).to(dev)
+        self._gen = torch.Generator(device=dev)
+        if seed is not None:
+            self._gen.manual_seed(int(seed))
+        self._shuffle = bool(shuffle)
+        self._order = torch.arange(n, device=dev)
+        if self._shuffle:
+            self._order = torch.randperm(n, device=dev, generator=self._gen)
+        self.epoch, self.dataStart, self.dataLength = 0, 0, n
+        self._step = 0
+        self.last_params = None
+
+    def getNextBatch(self, batchSizeof3DShape=32, imageSize=None, augmentation=True):
+        torch, A, L = self._torch, self._A, self._L
+        col, row = imageSize or (256, 256)                                   # (image_col, image_row), as dataLoaderSingleObject reads it
+        idx = self._order[self.dataStart:self.dataStart + batchSizeof3DShape]
+        self.dataStart += int(idx.numel())
+        if self.dataStart >= self.dataLength:
+            self.epoch += 1
+            self.dataStart = 0
+            if self._shuffle:
+                self._order = torch.randperm(self.dataLength, device=self._device, generator=self._gen)
+        params = A.draw_params(self._arena, self._image_index[idx], self._boxes[idx], augmentation, self._step)
+        self._step += 1
+        self.last_params = params
+        images = A.augment_images(self._arena, params, (row, col))
+        B = int(idx.numel())
+        out = torch.empty((B,) + self._sample_shape, dtype=torch.float32, device=self._device)
+        with torch.cuda.device(self._device):
+            st = L.ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        L.call('vv_unpack_bits_gather', L.ptr(self._packed), L.ptr(self._cad_index[idx].contiguous()), L.ptr(out), B, self._voxels, st)
+        sin = self._sin[idx].clone()
+        flipped = (params[:, A.P_FLIP] & 1) != 0
+        sin[:, 0] = torch.where(flipped, -sin[:, 0], sin[:, 0])              # azimuth -> -azimuth: the sine changes sign, the cosine does not
+        return self._inst[idx], self._cls[idx], sin, self._cos[idx], images, out
+
+
+# what the entry scripts' --loader names
+LOADERS = {'host': dataLoaderSingleObject, 'device': deviceDataLoaderSingleObject}

@@ -937,6 +937,8 @@ class nolboSingleObject(_PriorImageModel):
 
     def _prior_means(self, category_list, category_indices, inst_indices, training):
         """prior_cat [C, Lc] and the instance prior's means of each sample [B, I, Li] (nolbo.py:166-181)."""
+        if torch.is_tensor(category_list):                                 # a device loader's one-hots: one [B, C] copy to build the table's rows
+            category_list = category_list.detach().cpu().numpy()
         cat_l = np.asarray(np.array(category_list), dtype=np.float32)
         inst_ind = np.asarray(inst_indices, dtype=np.float32)
         B, I = cat_l.shape[0], inst_ind.shape[0]

@@ -5,6 +5,7 @@
     synthetic  seeded configs, weights and voxel batches (no dataset ships with the reference)
     tensor     DeviceArray, the np.array()-able handle the model API returns
     masks      KeepMasks: dropout / missing-latent masks drawn on the device from a counter-based generator, with a host twin
+    augment    ImageArena, draw_params, augment_images: Pascal3D image batches (crop, flip, colour, warp, cubic resize) built on the device
 """
 import os
 

@@ -169,6 +169,11 @@ SIGNATURES = {
     'vv_keep_mask': (_i, [_vp, _i, _i, _f, _u64, _u64, _vp]),
     'vv_keep_mask_host': (_i, [_vp, _i, _i, _f, _u64, _u64]),
     'vv_mask_scale': (_i, [_vp, _vp, _f, _vp, _i, _i, _vp]),
+    'vv_augment_images': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    'vv_augment_images_host': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp]),
+    'vv_augment_draw': (_i, [_vp, _i, _vp, _vp, _i, _i, _u64, _u64, _vp, _vp]),
+    'vv_augment_draw_host': (_i, [_vp, _i, _vp, _vp, _i, _i, _u64, _u64, _vp]),
+    'vv_augment_check_host': (_i, [_vp, _i, _vp, _i]),
 }
 
 

@@ -773,6 +773,44 @@ int vv_keep_mask(float *keep, int batch, int latent, float rate, unsigned long l
 int vv_keep_mask_host(float *keep, int batch, int latent, float rate, unsigned long long seed, unsigned long long offset);
 int vv_mask_scale(const float *x, const float *keep, float scale, float *y, int batch, int latent, void *hip_stream);
 
+/* ---- Pascal3D image batches built on the device (csrc/augment.h states every expression and the table of random draws): the
+ * reference's input pipeline, pascal3D.py:216-242 calling datasetUtils.py:91-152 -- crop the box with a random border, flip, Invert
+ * and Add per channel, cv2.warpAffine semantics with a random scale and translation (bilinear, constant border 0, the result held
+ * as an integer level), cv2.resize INTER_CUBIC semantics (half-pixel centres, Keys a = -0.75, replicate, no antialiasing), / 255.
+ * The function is defined in floating point (IEEE float64 for the warp and the cubic stage, written once for host and device); cv2's
+ * fixed-point coefficient tables are not modelled.  GaussianBlur and
+ * AddToHueAndSaturation are drawn (their slots stay fixed) and not applied.
+ *   images      one uint8 arena of HWC 3-channel images of differing sizes
+ *   image_meta  int64 [n_images][3] = (byte offset, rows, cols), rows and cols at most 16383
+ *   params      int32 [batch][16]: 0 image index; 1..4 crop row0, col0, rows h, cols w in the padded image's coordinates; 5 flip
+ *               bits (0 horizontal, 1 vertical); 6 scale as float32 bits; 7, 8 dRow, dCol; 9 invert bits per channel; 10..12
+ *               additive value per channel; 13, 14 rowPad, colPad (a zero border; coordinates outside the image read 0); 15 zero
+ *   out         float32 [batch][out_rows][out_cols][3], channel order as stored
+ * vv_augment_images: ONE launch on `hip_stream` for the batch, a workgroup per 16 x 16 output tile; the tile's footprint of warped
+ *   levels is built in LDS (48 KiB) and the cubic stage runs out of it; a tile whose footprint does not fit takes the direct
+ *   per-pixel form (csrc/augment.hip states the rule).  No workspace, no atomics: the same bits on every run.
+ * vv_augment_images_host: the same code on host pointers, no stream; bit for bit the device's output.
+ * vv_augment_draw: params rows from (image_index [batch], boxes [batch][4] = colMin, rowMin, colMax, rowMax float32) on
+ *   Philox4x32-10 (csrc/keep_mask.h): sample b owns blocks 8b .. 8b+7 of counter (blk, offset) under key seed.  augmentation = 0:
+ *   border 0.1, no flip, scale 1, no translation, no colour change.  One launch, a thread per sample.
+ * vv_augment_draw_host: the same on host pointers; bit for bit the device's rows.
+ * vv_augment_check_host: the admissibility of params rows against image_meta alone (host pointers).
+ * Refused before any launch: a NULL pointer (VV_ERR_NULL); n_images < 1, batch < 1 (images: > 65535), out_rows or out_cols < 1 or
+ * > 32767 (VV_ERR_SHAPE); a pointer below its element's alignment (VV_ERR_ALIGN).  The host entries also refuse, with VV_ERR_SHAPE
+ * and before anything is written by vv_augment_images_host: an image index outside n_images, h or w < 1, a crop outside the padded
+ * image, a scale that is not positive and finite, a box whose crop is empty.  The device entries cannot read params without a round
+ * trip: there a refused row's workgroups write nothing, and vv_augment_draw marks a refused sample's row (word 0 = -1) so that
+ * vv_augment_images leaves its output untouched. */
+int vv_augment_images(const unsigned char *images, const long long *image_meta, int n_images, const int *params, int batch,
+                      int out_rows, int out_cols, float *out, void *hip_stream);
+int vv_augment_images_host(const unsigned char *images, const long long *image_meta, int n_images, const int *params, int batch,
+                           int out_rows, int out_cols, float *out);
+int vv_augment_draw(const long long *image_meta, int n_images, const int *image_index, const float *boxes, int batch,
+                    int augmentation, unsigned long long seed, unsigned long long offset, int *params, void *hip_stream);
+int vv_augment_draw_host(const long long *image_meta, int n_images, const int *image_index, const float *boxes, int batch,
+                         int augmentation, unsigned long long seed, unsigned long long offset, int *params);
+int vv_augment_check_host(const long long *image_meta, int n_images, const int *params, int batch);
+
 #ifdef __cplusplus
 }
 #endif
