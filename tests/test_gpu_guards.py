@@ -21,6 +21,7 @@ import test_gpu_latent_ops as LO
 import test_gpu_ops as O
 import test_gpu_sampled as S
 import test_gpu_train_ops as TO
+import test_gpu_wgrad_exact as WX
 
 LEFT_OUT = {
     'vv_pr_curve_accumulate': 'tests/test_gpu_prcurve.py already runs it between sentinels, accumulators and workspace included',
@@ -184,6 +185,11 @@ for adt, gdt in (('f32', 'f32'), ('bf16', 'bf16'), ('bf16', 'f32')):     # dense
 row(O.test_wgrad_conv_phase_form, 'B,side,cin,cout', (1, 32, 64, 128), ['vv_wgrad_conv_k4s2'], 'B = 1, phase and reduction-GEMM forms')
 row(O.test_wgrad_conv_phase_form, 'B,side,cin,cout', (5, 16, 64, 128), ['vv_wgrad_conv_k4s2'], 'B = 5: the last box half empty')
 row(O.test_wgrad_conv_phase_form, 'B,side,cin,cout', (17, 8, 64, 128), ['vv_wgrad_conv_k4s2'], 'B = 17: NS = 16 samples per box + 1')
+# kernel forms only the exact tests reach (tests/test_gpu_wgrad_exact.py): a pitched A on either kernel, the full-tile single-channel bf16 kernel, side 2
+for dt in ('f32', 'bf16'):
+    row(WX.test_wgrad_dense_exact, 'rows,m,n,lda,adt,gdt', (300, 160, 96, 192, dt, dt), ['vv_wgrad_dense'], 'lda = 192 against m = 160: the last row ends 32 elements before the buffer does')
+    row(WX.test_wgrad_conv_exact, 'B,side,cin,cout,sdt,gdt', (5, 2, 64, 64, dt, dt), ['vv_wgrad_conv_k4s2'], 'side 2: five rows, half the taps of every row are padding')
+row(WX.test_wgrad_conv_exact, 'B,side,cin,cout,sdt,gdt', (2, 8, 1, 128, 'f32', 'bf16'), ['vv_wgrad_conv_k4s2'], 'one source channel, cout 128: shifted 16-byte loads at both ends of a grid row')
 row(TO.test_adam_step_against_float64, 'n,t,layer', (1, 1, False), ['vv_adam_step'], 'one element')
 row(TO.test_adam_step_against_float64, 'n,t,layer', (257, 2, False), ['vv_adam_step'], 'a block + 1')
 row(TO.test_adam_step_against_float64, 'n,t,layer', (16385, 7, True), ['vv_adam_step'], 'a 16384-element chunk + 1')

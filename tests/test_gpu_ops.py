@@ -9,6 +9,7 @@ import torch
 
 import _layer_calls as LC
 import _tol as T
+from _wgrad_inputs import wgrad_conv_ref as _wgrad_conv_ref
 from oracle import numpy_oracle as no
 
 pytestmark = pytest.mark.gpu
@@ -609,21 +610,6 @@ def test_lrelu_through_every_act_dispatch(L, entry, monkeypatch):
     _LRELU_CASES[entry](L, monkeypatch)
 
 
-def _wgrad_conv_ref(src, g):
-    """dW[t][ci][co] = sum over (b, o) of src[b, 2o-1+t, ci] * g[b, o, co] (zero padding), float64."""
-    B, S, _, _, cin = src.shape
-    o, cout = S // 2, g.shape[-1]
-    p = np.zeros((B, S + 2, S + 2, S + 2, cin))
-    p[:, 1:-1, 1:-1, 1:-1] = src
-    dw = np.zeros((4, 4, 4, cin, cout))
-    for td in range(4):
-        for th in range(4):
-            for tw in range(4):
-                win = p[:, td:td + 2 * o:2, th:th + 2 * o:2, tw:tw + 2 * o:2]          # [B,o,o,o,cin]
-                dw[td, th, tw] = np.einsum('bdhwi,bdhwo->io', win, g)
-    return dw
-
-
 @pytest.mark.parametrize('adt,gdt', [('f32', 'f32'), ('bf16', 'bf16'), ('bf16', 'f32')])
 def test_wgrad_kernels(L, adt, gdt, monkeypatch):
     """Weight gradients dW = A^T G: float32 operands on the exact-f32 MFMA, bf16 operands on the bf16 MFMA with
@@ -733,7 +719,7 @@ def test_batchnorm_train_ops(L, dtname, rows, C):
     assert np.abs(o['dgamma'].cpu().numpy() - dgamma).max() <= tol * max(1.0, np.abs(dgamma).max())
     if dtname == 'f32':
         _check(dx, dx_ref, 'f32', 'bn_act_bwd')
-    else:                                             # backward ops are pinned against float64 autograd in test_gpu_train_ops.py
+    else:                                             # per element and per act code: test_gpu_train_ops.py::test_bn_act_bwd_against_float64
         err = np.abs(dx.float().cpu().numpy().astype(np.float64) - dx_ref).max()
         assert err <= 2e-2 * np.abs(dx_ref).max() + 2e-2, ('bn_act_bwd bf16', err)
     if dtname == 'bf16':

@@ -10,6 +10,8 @@ import torch
 
 from oracle import numpy_oracle as no
 
+import _bn_inputs as BI
+import _tol as T
 from _train_ref import ADAM_B1, ADAM_B2, ADAM_CHUNK, ADAM_EPS, ADAM_UNITS, adam_units, lr_t_of
 
 pytestmark = pytest.mark.gpu
@@ -37,24 +39,30 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV).contiguous()
 
 
-def _guarded(a, lead=0):
-    """Device copy of `a` with `lead` sentinel floats in front (moves the payload off 16-byte alignment) and PAD behind.
-    Returns (whole buffer, payload view)."""
+def _guarded(a, lead=0, dtype=torch.float32):
+    """Device copy of `a` with `lead` sentinel elements in front (moves the payload off 16-byte alignment) and PAD behind.
+    Returns (whole buffer, payload view).  The sentinel is a bf16 value as well."""
     a = np.ascontiguousarray(a, dtype=np.float32).ravel()
-    buf = torch.full((lead + a.size + PAD,), SENTINEL, dtype=torch.float32, device=DEV)
+    buf = torch.full((lead + a.size + PAD,), SENTINEL, dtype=dtype, device=DEV)
     view = buf[lead:lead + a.size]
     view.copy_(torch.from_numpy(a))
     return buf, view
 
 
-def _guarded_empty(n, lead=0):
-    buf = torch.full((lead + n + PAD,), SENTINEL, dtype=torch.float32, device=DEV)
+def _guarded_empty(n, lead=0, dtype=torch.float32):
+    buf = torch.full((lead + n + PAD,), SENTINEL, dtype=dtype, device=DEV)
     return buf, buf[lead:lead + n]
 
 
+def _guarded_nan(n, dtype=torch.float32):
+    """An output: the payload pre-filled with NaN, so that an element the kernel leaves out fails every comparison."""
+    buf, view = _guarded_empty(n, 0, dtype)
+    view.fill_(float('nan'))
+    return buf, view
+
+
 def _canaries_intact(buf, lead, n):
-    b = buf.cpu().numpy()
-    return bool(np.all(b[:lead] == SENTINEL) and np.all(b[lead + n:] == SENTINEL))
+    return bool((buf[:lead] == SENTINEL).all().item() and (buf[lead + n:] == SENTINEL).all().item())
 
 
 # ------------------------------------------------------------------------------------------------------------ Adam
@@ -446,6 +454,139 @@ def test_sigmoid_f32_against_float64(L, in_place):
     # normal float32 (x < -87.3, where exp(-x) nears or passes the float32 range) the result may be flushed to 0
     assert np.all(np.abs(got.astype(np.float64) - ref) <= 4 * 2.0 ** -23 * ref + TINY)
     assert got[x == 0].tolist() == [0.5] * int((x == 0).sum())
+
+
+# ---------------------------------------------------------------------------- BatchNorm training ops and the column sum
+# Inputs, references and the derivation of every bound: tests/_bn_inputs.py (host self-test in tests/test_tol_host.py).
+_TDT = {'f32': torch.float32, 'bf16': torch.bfloat16}
+
+
+def _bn_ws(L, rows, C):
+    return torch.empty(max(L.load().vv_bn_workspace_bytes(rows, C), 16), dtype=torch.uint8, device=DEV)
+
+
+def _within(got, ref, bound, what):
+    """|got - ref| <= bound for every element (a NaN is over the bound) -> worst err / bound."""
+    got, ref, bound = np.asarray(got, np.float64).ravel(), np.asarray(ref, np.float64).ravel(), np.asarray(bound, np.float64).ravel()
+    err = np.abs(got - ref)
+    bad = ~(err <= bound)
+    if bad.any():
+        i = int(np.argmax(np.where(bad, np.nan_to_num(err, nan=np.inf), -1.0)))
+        raise AssertionError('%s: %d of %d elements over the bound; worst at %d: got %r ref %r err %.3e bound %.3e' % (
+            what, int(bad.sum()), bad.size, i, got[i], ref[i], err[i], bound[i]))
+    live = bound > 0
+    return float((err[live] / bound[live]).max()) if live.any() else 0.0
+
+
+@pytest.mark.parametrize('dtname,rows,C', BI.BN_STATS_CASES)
+def test_bn_train_stats_on_integer_inputs(L, dtname, rows, C):
+    """vv_bn_train_stats where the sums of x and x^2 are exact: the mean equals float32(s / R), the variance is within one float32
+    spacing of float32(ss / R - m m), rstd / scale / shift and the moving statistics within the unit counts of _bn_inputs.stats_ref.
+    C / V = 96, 65, 86, 255 leave threads of the workgroup without a row; rows go from one to past the 1024-block cap.
+    Measured, worst err / bound over all cases: mean and var 0 (equal), rstd 0.49, scale 0.61, shift 0.48, moving statistics 0.49."""
+    d = BI.inputs(rows, C)
+    (ref, _, _) = BI.stats_ref(d)
+    xb, xd = _guarded(d.x, dtype=_TDT[dtname])
+    ins = {n: _guarded(getattr(d, n)) for n in ('gamma', 'beta')}
+    mov = {'moving_mean': _guarded(d.mm0), 'moving_var': _guarded(d.mv0)}
+    outs = {n: _guarded_nan(C) for n in ('mean', 'var', 'rstd', 'scale', 'shift')}
+    ws = _bn_ws(L, rows, C)
+    L.call('vv_bn_train_stats', L.ptr(xd), rows, C, L.ptr(ins['gamma'][1]), L.ptr(ins['beta'][1]), BI.EPS, BI.MOMENTUM, L.ptr(outs['mean'][1]),
+           L.ptr(outs['var'][1]), L.ptr(outs['rstd'][1]), L.ptr(outs['scale'][1]), L.ptr(outs['shift'][1]), L.ptr(mov['moving_mean'][1]),
+           L.ptr(mov['moving_var'][1]), L.DTYPES[dtname], L.ptr(ws), ws.numel(), _st())
+    torch.cuda.synchronize()
+    assert _canaries_intact(xb, 0, rows * C) and np.array_equal(xd.float().cpu().numpy().reshape(rows, C), d.x)
+    for n, (buf, view) in list(ins.items()) + list(mov.items()) + list(outs.items()):
+        assert _canaries_intact(buf, 0, C), n
+    worst = {}
+    for n in ('mean', 'var', 'rstd', 'scale', 'shift', 'moving_mean', 'moving_var'):
+        got = (outs.get(n) or mov.get(n))[1].cpu().numpy()
+        worst[n] = _within(got, ref[n][0], ref[n][1], 'bn_train_stats %s %s rows=%d C=%d' % (n, dtname, rows, C))
+    print('\n[bn stats %s rows=%d C=%d] worst err / bound: %s' % (dtname, rows, C, ' '.join('%s %.2f' % kv for kv in worst.items())))
+
+
+@pytest.mark.parametrize('dtname,rows,C,act', BI.BN_ACT_CASES)
+def test_bn_act_fwd_against_float64(L, dtname, rows, C, act):
+    """vv_bn_act_fwd for every activation code.  Identity, ReLU and LeakyReLU are exact on these inputs (check_exact); ELU is held to
+    one rounding per element.  Elements with u == 0 exist and are pinned: 0 for every code (ReLU `v > 0 ? v : 0`, LeakyReLU 0.3 * 0,
+    ELU expm1(0))."""
+    d = BI.inputs(rows, C)
+    u, ref = BI.act_fwd_ref(d, act, dtname)
+    xb, xd = _guarded(d.x, dtype=_TDT[dtname])
+    (sb, sd), (hb, hd) = _guarded(d.scale), _guarded(d.shift)
+    yb, yd = _guarded_nan(rows * C, _TDT[dtname])
+    L.call('vv_bn_act_fwd', L.ptr(xd), L.ptr(sd), L.ptr(hd), L.ptr(yd), rows, C, act, L.DTYPES[dtname], _st())
+    torch.cuda.synchronize()
+    assert _canaries_intact(xb, 0, rows * C) and _canaries_intact(yb, 0, rows * C) and _canaries_intact(sb, 0, C) and _canaries_intact(hb, 0, C)
+    y = yd.float().cpu().numpy().reshape(rows, C)
+    what = 'bn_act_fwd act=%d %s rows=%d C=%d' % (act, dtname, rows, C)
+    if act == 1:
+        T.check_one_rounding(y, ref, u, dtname, what)
+    else:
+        T.check_exact(y, ref, what)
+    at0 = u == 0
+    assert at0[0, ::4].all() and not y[at0].any(), what                                      # the value at u == 0
+
+
+@pytest.mark.parametrize('dtname,rows,C,act', BI.BN_ACT_CASES)
+def test_bn_act_bwd_against_float64(L, dtname, rows, C, act):
+    """vv_bn_act_bwd for every activation code, on statistics the test supplies (mean an integer, rstd = 1/2, scale +-2^k, shift an
+    integer).  Identity and ReLU: dbeta and dgamma EQUAL the float64 sums.  LeakyReLU and ELU: per channel within
+    U sum |term| (k + c + e), k the longest chain of float32 additions (_bn_inputs.reduce_chain, act_bwd_ref).  dx per element against
+    float64 from the device's own dgamma / dbeta: 3 float32 ulps of |scale| (|du| + |k1| + |x - mean| |k2|) (_bn_inputs.dx_ref), bf16
+    one rounding on top of the float32 term of those three.  The derivative at u == 0 is part of every reference: 1 for identity
+    and ELU (exp(0)), 0 for ReLU, 0.3 for LeakyReLU; dy is never 0, so another value there moves dx by |scale dy| times the difference.
+    bf16 runs ELU on bn_reduce_kernel<1, T, ELU> and the other three codes on the run-time switch.
+    Measured, worst err / bound over all cases: the sums of LeakyReLU 0.26 (f32) / 0.27 (bf16), of ELU 0.34 (f32) / 0.82 (bf16, a one-row
+    case: the bound is __expf's alone there); dx 0.42 (f32), 0.99 (bf16: an element next to a rounding boundary takes the whole half ulp)."""
+    d = BI.inputs(rows, C)
+    du, dbeta, dgamma, bound_b, bound_g = BI.act_bwd_ref(d, act, dtname)
+    tdt = _TDT[dtname]
+    (xb, xd), (gb, gd) = _guarded(d.x, dtype=tdt), _guarded(d.dy, dtype=tdt)
+    par = {n: _guarded(getattr(d, n)) for n in ('scale', 'shift', 'mean', 'rstd')}
+    outs = {n: _guarded_nan(C) for n in ('dgamma', 'dbeta')}
+    ob, od = _guarded_nan(rows * C, tdt)
+    ws = _bn_ws(L, rows, C)
+    L.call('vv_bn_act_bwd', L.ptr(xd), L.ptr(gd), L.ptr(par['scale'][1]), L.ptr(par['shift'][1]), L.ptr(par['mean'][1]), L.ptr(par['rstd'][1]),
+           L.ptr(outs['dgamma'][1]), L.ptr(outs['dbeta'][1]), L.ptr(od), rows, C, act, L.DTYPES[dtname], L.ptr(ws), ws.numel(), _st())
+    torch.cuda.synchronize()
+    for buf in (xb, gb, ob):
+        assert _canaries_intact(buf, 0, rows * C)
+    for n, (buf, view) in list(par.items()) + list(outs.items()):
+        assert _canaries_intact(buf, 0, C), n
+    what = 'bn_act_bwd act=%d %s rows=%d C=%d' % (act, dtname, rows, C)
+    got_b, got_g = outs['dbeta'][1].cpu().numpy(), outs['dgamma'][1].cpu().numpy()
+    u = BI.pre_act(d)
+    at0 = u == 0
+    assert at0[0, ::4].all() and np.array_equal(BI.act_grad(u, act)[at0], np.full(int(at0.sum()), BI.ACT_GRAD_AT_0[act]))
+    if act in (0, 2):
+        T.check_exact(got_b, dbeta, what + ' dbeta')
+        T.check_exact(got_g, dgamma, what + ' dgamma')
+    else:
+        rb, rg = _within(got_b, dbeta, bound_b, what + ' dbeta'), _within(got_g, dgamma, bound_g, what + ' dgamma')
+        print('\n[%s] chain k = %d, worst err / bound: dbeta %.3f dgamma %.3f' % (what, BI.reduce_chain(rows, C, dtname), rb, rg))
+    ref, terms = BI.dx_ref(d, du, got_g, got_b)
+    dx = od.float().cpu().numpy().reshape(rows, C)
+    if dtname == 'f32':
+        r = _within(dx, ref, 3 * 2.0 ** -23 * (np.abs(terms[0]) + np.abs(terms[1]) + np.abs(terms[2])), what + ' dx')
+    else:
+        r = T.check_one_rounding(dx, ref, np.stack(terms), 'bf16', what + ' dx')
+    print('\n[%s] dx worst err / bound %.3f' % (what, r))
+
+
+@pytest.mark.parametrize('dtname', ['f32', 'bf16'])
+@pytest.mark.parametrize('C', BI.COLSUM_C)
+@pytest.mark.parametrize('rows', BI.COLSUM_ROWS)
+def test_colsum_exact(L, dtname, rows, C):
+    """vv_colsum on integers -4..4 (sums below 2^24: exact in any order): equality with the float64 sum, around the 8 row slices and
+    the 32-row trip of colsum_kernel, with one column, a partial and a second column block."""
+    x = BI.colsum_inputs(rows, C)
+    xb, xd = _guarded(x, dtype=_TDT[dtname])
+    ob, out = _guarded_nan(C)
+    L.call('vv_colsum', L.ptr(xd), L.ptr(out), rows, C, L.DTYPES[dtname], _st())
+    torch.cuda.synchronize()
+    assert _canaries_intact(xb, 0, rows * C) and _canaries_intact(ob, 0, C)
+    T.check_exact(out, x.astype(np.float64).sum(0), 'colsum %s rows=%d C=%d' % (dtname, rows, C))
 
 
 # ------------------------------------------------------------------------------------------------------- argument checks

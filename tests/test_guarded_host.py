@@ -149,6 +149,19 @@ def test_every_row_is_a_case_of_an_oracle_parity_test():
         assert r.tail.strip(), r.id                                 # every row says what makes it a tail (or that it is the B = 1 case)
 
 
+def test_the_wgrad_forms_only_the_exact_tests_reach_have_rows():
+    """A pitched A (lda != m) on the float32 and on the bf16 kernel, the single-channel bf16 kernel at its full tile (cout > 64) and
+    source side 2 are launched by tests/test_gpu_wgrad_exact.py alone; each has a row, and each row is a case of that file's tables."""
+    T = importlib.import_module('test_gpu_guards')
+    WI = importlib.import_module('_wgrad_inputs')
+    dense = [tuple(r.case.values()) for r in T.ROWS if r.test.__name__ == 'test_wgrad_dense_exact']
+    conv = [tuple(r.case.values()) for r in T.ROWS if r.test.__name__ == 'test_wgrad_conv_exact']
+    assert set(dense) <= set(WI.DENSE_CASES) and set(conv) <= set(WI.CONV_CASES)
+    assert {WI.dense_route(c)[0] for c in dense if c[3] != c[1]} == {'f32', 'bf16'}
+    assert any(WI.conv_route(c)[0] == 'bf16 one channel, full tile' for c in conv)
+    assert {WI.conv_route(c)[0] for c in conv if c[1] == 2} == {'f32', 'bf16'}
+
+
 # ------------------------------------------------------------ the recorder and the replayer, on a stand-in library of numpy "kernels"
 class _FakeLib:
     """voxvae.lib's surface (ptr, call, load, HOOK_VARS) over two entries of the real header computed by numpy through raw host pointers;
