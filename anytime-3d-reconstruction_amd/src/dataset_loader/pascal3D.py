@@ -83,9 +83,13 @@ class deviceDataLoaderSingleObject(object):
     The synthetic stand-in serves seeded "photos": uint8 images of differing sizes, one per object, with a box; the object's three
     max-projections are pasted at the box over a seeded textured background, so crop, border and warp all matter.  `from_arrays` takes
     decoded data instead.  The draws are a pure function of (voxvae.manual_seed's seed, rank, step): voxvae/augment.py; `last_params` holds
-    the rows of the last batch.  GaussianBlur and AddToHueAndSaturation are drawn and not applied (csrc/augment.h)."""
+    the rows of the last batch.  colour_ops='invert_add' (the default) applies Invert and Add, as this loader always did; colour_ops='all'
+    applies the reference's four -- GaussianBlur, Invert, Add, AddToHueAndSaturation, in that order -- through the colour table of
+    csrc/augment.h (`last_colour` holds its rows; the geometry and the Invert / Add draws are the same under both settings)."""
 
-    def __init__(self, trainOrVal='train', Pascal3DDataPath=None, voxel=64, instances=None, device=None, seed=None):
+    COLOUR_OPS = ('invert_add', 'all')
+
+    def __init__(self, trainOrVal='train', Pascal3DDataPath=None, voxel=64, instances=None, device=None, seed=None, colour_ops='invert_add'):
         n = 256 if trainOrVal == 'train' else 96
         if isinstance(Pascal3DDataPath, str) and Pascal3DDataPath.startswith('synthetic:'):
             parts = Pascal3DDataPath.split(':')
@@ -102,18 +106,18 @@ class deviceDataLoaderSingleObject(object):
         insts = None if instances is None else np.random.default_rng(data_seed + 1).integers(0, int(instances), n)
         images, boxes = self._photos(voxels, np.random.default_rng(data_seed + 2))
         self._setup(images, boxes, classes, np.arange(n), euler, voxels, insts, instances, None, device,
-                    data_seed if seed is None else seed, trainOrVal == 'train')
+                    data_seed if seed is None else seed, trainOrVal == 'train', colour_ops)
 
     @classmethod
     def from_arrays(cls, images, boxes, classes, cad_index, euler, cad_grids, inst_index=None, instances=None, image_index=None, device=None,
-                    seed=None, shuffle=True):
+                    seed=None, shuffle=True, colour_ops='invert_add'):
         """images: uint8 [rows, cols, 3] arrays; boxes [n, 4] = (colMin, rowMin, colMax, rowMax) in pixels; classes [n] in 0 .. 11;
         cad_index [n] rows of cad_grids [m, D, D, D] (occupancy, binarised at 0.5); euler [n, 3] = (azimuth, elevation, in-plane
         rotation) in radians.  image_index [n] (default: object i is in image i) lets several objects share a photo; instances with
         inst_index (default cad_index) makes instList the one-hot [n, instances], otherwise it is the [n, 1] zeros."""
         self = cls.__new__(cls)
         insts = None if instances is None else np.asarray(cad_index if inst_index is None else inst_index)
-        self._setup(images, boxes, classes, cad_index, euler, cad_grids, insts, instances, image_index, device, seed, shuffle)
+        self._setup(images, boxes, classes, cad_index, euler, cad_grids, insts, instances, image_index, device, seed, shuffle, colour_ops)
         return self
 
     @staticmethod
@@ -136,7 +140,11 @@ class deviceDataLoaderSingleObject(object):
             boxes[i] = (c0 + f[0], r0 + f[1], c0 + bw - f[2], r0 + bh - f[3])
         return images, boxes
 
-    def _setup(self, images, boxes, classes, cad_index, euler, cad_grids, insts, instances, image_index, device, seed, shuffle):
+    def _setup(self, images, boxes, classes, cad_index, euler, cad_grids, insts, instances, image_index, device, seed, shuffle,
+               colour_ops='invert_add'):
+        if colour_ops not in self.COLOUR_OPS:
+            raise ValueError('colour_ops must be one of %s, got %r' % (self.COLOUR_OPS, colour_ops))
+        self.colour_ops = colour_ops
         import torch
         import voxvae
         from voxvae import augment as _A
@@ -184,7 +192,7 @@ class deviceDataLoaderSingleObject(object):
             self._order = torch.randperm(n, device=dev, generator=self._gen)
         self.epoch, self.dataStart, self.dataLength = 0, 0, n
         self._step = 0
-        self.last_params = None
+        self.last_params = self.last_colour = None
 
     def getNextBatch(self, batchSizeof3DShape=32, imageSize=None, augmentation=True):
         torch, A, L = self._torch, self._A, self._L
@@ -196,10 +204,14 @@ class deviceDataLoaderSingleObject(object):
             self.dataStart = 0
             if self._shuffle:
                 self._order = torch.randperm(self.dataLength, device=self._device, generator=self._gen)
-        params = A.draw_params(self._arena, self._image_index[idx], self._boxes[idx], augmentation, self._step)
+        colour = None
+        if self.colour_ops == 'all':
+            params, colour = A.draw_params(self._arena, self._image_index[idx], self._boxes[idx], augmentation, self._step, colour=True)
+        else:
+            params = A.draw_params(self._arena, self._image_index[idx], self._boxes[idx], augmentation, self._step)
         self._step += 1
-        self.last_params = params
-        images = A.augment_images(self._arena, params, (row, col))
+        self.last_params, self.last_colour = params, colour
+        images = A.augment_images(self._arena, params, (row, col), colour=colour)
         B = int(idx.numel())
         out = torch.empty((B,) + self._sample_shape, dtype=torch.float32, device=self._device)
         with torch.cuda.device(self._device):
@@ -213,3 +225,15 @@ class deviceDataLoaderSingleObject(object):
 
 # what the entry scripts' --loader names
 LOADERS = {'host': dataLoaderSingleObject, 'device': deviceDataLoaderSingleObject}
+
+
+def loader_factory(loader, colour_ops='invert_add'):
+    """The class behind --loader, with --colour-ops bound to it: 'all' exists on the device loader only (the host class serves
+    projections with noise, no photo chain)."""
+    cls = LOADERS[loader]
+    if colour_ops == 'invert_add':
+        return cls
+    if loader != 'device':
+        raise ValueError("colour_ops=%r needs the device loader (--loader device)" % (colour_ops,))
+    import functools
+    return functools.partial(cls, colour_ops=colour_ops)

@@ -46,10 +46,10 @@ def train(
         save_path=None, load_path=None,
         load_encoder_backbone_path=None, load_encoder_backbone_name=None,
         load_decoder_path=None, load_decoder_name=None,
-        batch_size=72, image_size=(256, 256), max_iter=None, dataset_path=None, loader='host',
+        batch_size=72, image_size=(256, 256), max_iter=None, dataset_path=None, loader='host', colour_ops='invert_add',
 ):
     import src.module.nolbo as nolbo
-    make_loader = pascal3D.LOADERS[loader]
+    make_loader = pascal3D.loader_factory(loader, colour_ops)
     model = nolbo.nolboSingleObject(nolbo_structure=config, backbone_style=Darknet.Darknet19, learning_rate=learning_rate)
     voxel, idx = config['decoder']['output_shape'][0], indices_of(config)
     instances = idx['inst_indices'].shape[0]
@@ -111,8 +111,10 @@ if __name__ == '__main__':
     ap.add_argument('--dataset-path', default=None)
     ap.add_argument('--loader', choices=('host', 'device'), default='host',
                     help="'device': pascal3D.deviceDataLoaderSingleObject builds the image batch on the GPU")
+    ap.add_argument('--colour-ops', choices=('invert_add', 'all'), default='invert_add',
+                    help="with --loader device: 'all' also applies GaussianBlur and AddToHueAndSaturation, the reference's other two")
     a = ap.parse_args()
     voxvae.set_default_dtype('f32')        # the 2D encoder trains by float32 autograd
     sys.exit(0 if train(training_epoch=a.epochs, learning_rate=a.lr, config=make_config(a.latent, a.voxel), save_path=a.save_path,
                         load_path=a.load_path, batch_size=a.batch, image_size=(a.image, a.image), max_iter=a.max_iter,
-                        dataset_path=a.dataset_path, loader=a.loader) is not None else 1)
+                        dataset_path=a.dataset_path, loader=a.loader, colour_ops=a.colour_ops) is not None else 1)

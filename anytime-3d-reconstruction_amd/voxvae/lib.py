@@ -174,6 +174,11 @@ SIGNATURES = {
     'vv_augment_draw': (_i, [_vp, _i, _vp, _vp, _i, _i, _u64, _u64, _vp, _vp]),
     'vv_augment_draw_host': (_i, [_vp, _i, _vp, _vp, _i, _i, _u64, _u64, _vp]),
     'vv_augment_check_host': (_i, [_vp, _i, _vp, _i]),
+    'vv_augment_draw_ex': (_i, [_vp, _i, _vp, _vp, _i, _i, _u64, _u64, _vp, _vp, _vp]),
+    'vv_augment_draw_ex_host': (_i, [_vp, _i, _vp, _vp, _i, _i, _u64, _u64, _vp, _vp]),
+    'vv_augment_colour_workspace_bytes': (_sz, [_i, _i, _i]),
+    'vv_augment_images_ex': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    'vv_augment_images_ex_host': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _i]),
 }
 
 

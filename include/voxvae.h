@@ -778,8 +778,9 @@ int vv_mask_scale(const float *x, const float *keep, float scale, float *y, int 
  * and Add per channel, cv2.warpAffine semantics with a random scale and translation (bilinear, constant border 0, the result held
  * as an integer level), cv2.resize INTER_CUBIC semantics (half-pixel centres, Keys a = -0.75, replicate, no antialiasing), / 255.
  * The function is defined in floating point (IEEE float64 for the warp and the cubic stage, written once for host and device); cv2's
- * fixed-point coefficient tables are not modelled.  GaussianBlur and
- * AddToHueAndSaturation are drawn (their slots stay fixed) and not applied.
+ * fixed-point coefficient tables are not modelled.  The entries below apply Invert and Add, as they always did; GaussianBlur and
+ * AddToHueAndSaturation (datasetUtils.py:64-89, the other two of imgAug's four) are applied by the _ex entries further down, per
+ * sample and opt-in through a second table.
  *   images      one uint8 arena of HWC 3-channel images of differing sizes
  *   image_meta  int64 [n_images][3] = (byte offset, rows, cols), rows and cols at most 16383
  *   params      int32 [batch][16]: 0 image index; 1..4 crop row0, col0, rows h, cols w in the padded image's coordinates; 5 flip
@@ -810,6 +811,44 @@ int vv_augment_draw(const long long *image_meta, int n_images, const int *image_
 int vv_augment_draw_host(const long long *image_meta, int n_images, const int *image_index, const float *boxes, int batch,
                          int augmentation, unsigned long long seed, unsigned long long offset, int *params);
 int vv_augment_check_host(const long long *image_meta, int n_images, const int *params, int batch);
+
+/* ---- All four colour operations of the reference's imgAug (datasetUtils.py:64-89 builds iaa.Sequential([GaussianBlur(sigma=(0, 3.0)),
+ * Invert(0.05, per_channel=True), Add((-10, 10), per_channel=0.5), AddToHueAndSaturation((-20, 20))]), each gated by :98-103) on the
+ * flipped crop, in that order: blur -> invert -> add -> hue/saturation.  csrc/augment.h 1a and 1b state both new stages: the blur is
+ * scipy.ndimage.gaussian_filter(mode='mirror', truncate 4) in float64 with one rounding at the end and weights from the header's own
+ * exponential; hue/saturation goes through OpenCV's 8-bit HSV (integer forward, float32 inverse) with channel 0 taken as R.  Not
+ * modelled: scipy's summation order, cv2.GaussianBlur's fixed-point path, and the agreement of the HSV chain with cv2 is not measured.
+ *   colour      int32 [batch][4]: 0 flags (bit 0 blur, bit 1 hue/saturation); 1 sigma as float32 bits, 0 <= sigma <= 16; 2 hue add
+ *               in H units, -179 .. 179; 3 saturation add, -255 .. 255.  A row of zeros is vv_augment_images' result bit for bit.
+ *   workspace   vv_augment_colour_workspace_bytes(max_rows, max_cols, batch) bytes (pure host arithmetic; 0 for arguments out of
+ *               range): one slab of max_rows * max_cols 32-bit words per sample, sample b owns slab b.  Written before it is read;
+ *               the result does not depend on workspace_bytes beyond that minimum.
+ * vv_augment_draw_ex (replaces datasetUtils.py:98-103's choice of the four and imgaug's draws of sigma and value): vv_augment_draw's
+ *   launch, which also fills `colour` from the same Philox blocks (slots 4, 6, 20, 21); the params rows are vv_augment_draw's bit for
+ *   bit.  augmentation = 0 and a refused sample: a colour row of zeros.
+ * vv_augment_images_ex (replaces datasetUtils.py:64-89 and :101-103 in front of :137-152): TWO launches on `hip_stream`.  The colour
+ *   pre-pass, 32 x 32 tiles of a flagged sample's crop (as many workgroups per sample as a max_rows x max_cols crop has tiles, each
+ *   sample's workgroups walking that sample's own tiles: h * w alone decides whether a crop fits), writes the finished source
+ *   levels into the sample's slab; then vv_augment_images' kernel, reading a flagged sample's source from its slab.  colour == NULL is
+ *   vv_augment_images.
+ * The _host entries are the same code on host pointers (the workspace too), bit for bit the device's output.
+ * Refused before any launch, besides what vv_augment_images / vv_augment_draw refuse: workspace or (draw) colour NULL (VV_ERR_NULL);
+ *   max_rows or max_cols < 1 or > 32767 (VV_ERR_SHAPE); workspace_bytes below the minimum (VV_ERR_WORKSPACE).  A row is inadmissible
+ *   when its params row is, when its colour row is (other flag bits, sigma NaN, negative or above 16, hue or saturation out of range),
+ *   or when it has a flag set and h * w exceeds max_rows * max_cols: the host entry returns VV_ERR_SHAPE before anything is written;
+ *   on the device such a row's workgroups write nothing in either launch. */
+int vv_augment_draw_ex(const long long *image_meta, int n_images, const int *image_index, const float *boxes, int batch,
+                       int augmentation, unsigned long long seed, unsigned long long offset, int *params, int *colour,
+                       void *hip_stream);
+int vv_augment_draw_ex_host(const long long *image_meta, int n_images, const int *image_index, const float *boxes, int batch,
+                            int augmentation, unsigned long long seed, unsigned long long offset, int *params, int *colour);
+size_t vv_augment_colour_workspace_bytes(int max_rows, int max_cols, int batch);
+int vv_augment_images_ex(const unsigned char *images, const long long *image_meta, int n_images, const int *params, int batch,
+                         int out_rows, int out_cols, float *out, const int *colour, void *workspace, size_t workspace_bytes,
+                         int max_rows, int max_cols, void *hip_stream);
+int vv_augment_images_ex_host(const unsigned char *images, const long long *image_meta, int n_images, const int *params, int batch,
+                              int out_rows, int out_cols, float *out, const int *colour, void *workspace, size_t workspace_bytes,
+                              int max_rows, int max_cols);
 
 #ifdef __cplusplus
 }
