@@ -865,11 +865,12 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T *__restrict__ x, fl
 
 // Row blocks of the two BatchNorm sweeps: 256 rows per block on the long layers (at most 1024 blocks), but never fewer
 // blocks than keep ~16 rows per block -- a 2048-row x 512-channel layer is 128 blocks, not 8.
-// A thread owns V consecutive channels (4 floats / 8 bf16) and a workgroup spans whole rows: C % V == 0, C / V <= 256
+// A thread owns V consecutive channels (4 floats / 8 bf16) and a workgroup spans whole rows: C % V == 0, C / V <= 256.
+// C / V need not divide 256: the 256 % (C / V) threads behind the last whole row own no row (`rsub < rows_par` in every kernel) --
+// 192 channels are 24 bf16 vectors, 10 rows in parallel and 16 idle threads.
 inline bool bn_shape_ok(long rows, int channels, int dtype) {
     const int V = dtype == VV_BF16 ? 8 : 4;
-    if (rows <= 0 || channels <= 0 || channels % V || channels / V > 256) return false;
-    return channels / V >= 64 || 256 % (channels / V) == 0;
+    return rows > 0 && channels > 0 && channels % V == 0 && channels / V <= 256;
 }
 
 // Grid of the two element-wise sweeps: a block covers 256 / (C / V) rows per step; two steps per block on the short

@@ -101,6 +101,15 @@ def convT_route(side, cin, cout, dt, want_fp8, wide, sw):
     return 'igemm'
 
 
+def igemm_admits(cin, cout, dt):
+    """The channel rule of the implicit GEMM's stride-2 forms (run_igemm, igemm.hip): input channels a power-of-two multiple of the K
+    block (64 bf16 elements, 32 float32), output channels whole 16-byte stores (8 bf16, 4 float32).  The form every route function
+    falls back to, so a layer it does not admit has no kernel."""
+    bk, vec = (64, 8) if dt == L.VV_BF16 else (32, 4)
+    q = cin // bk
+    return cin > 0 and cin % bk == 0 and q & (q - 1) == 0 and cout > 0 and cout % vec == 0
+
+
 @functools.lru_cache(maxsize=None)
 def fused_tail(K5, E, Lz, lin, n1, variational, sw):
     """True when encoder tail -> reparam / KL -> Dense -> first decoder layer run as the fused launches of latent_tail.hip (bf16).  A pure

@@ -283,6 +283,7 @@ class Trainer:
         # gradients and the MFMA operands in bf16, float32 master weights / Adam moments / BatchNorm statistics / losses,
         # weight gradients accumulated in float32 (f32 MFMA over widened operands).
         self._init_forward(enc, dec, variational)     # enc None: decoder-only (image -> 3D model)
+        self._refuse_untrainable_widths()
         self.lr = float(learning_rate)
         self.world, self.group = int(world_size), group
         self.t = 0
@@ -326,6 +327,38 @@ class Trainer:
         self._prepacked = {}       # (direction, weight pointer, cin, cout) -> the step's batched 'skip' images (_prepack)
         self._adam_ptrs = None
         self._sumsq = None         # weight_l2 > 0: the per-chunk sum w^2 the last optimiser launch left
+
+    def _stride2_launches(self):
+        """The forward launch and the data gradient of every stride-2 layer of an optimisation step: (variable, which of the two,
+        direction, side, cin, cout), in model order.  A data gradient is the other direction's layer on the same array."""
+        out = []
+        if self.enc is not None:
+            fe, side = self.enc.filters, self.enc.D // 2
+            for i in range(1, len(fe) - 1):
+                out.append(('enc/conv%d/kernel' % i, 'forward layer', R.CONV, side, fe[i - 1], fe[i]))
+                out.append(('enc/conv%d/kernel' % i, 'data gradient', R.CONVT, side // 2, fe[i], fe[i - 1]))
+                side //= 2
+        fd, side = self.dec.filters, self.dec.S
+        for i in range(1, len(fd) - 1):
+            out.append(('dec/convT%d/kernel' % i, 'forward layer', R.CONVT, side, fd[i - 1], fd[i]))
+            out.append(('dec/convT%d/kernel' % i, 'data gradient', R.CONV, 2 * side, fd[i], fd[i - 1]))
+            side *= 2
+        return out
+
+    def _refuse_untrainable_widths(self):
+        """A model whose step would fail half way is refused when the Trainer is built.  The data gradient of a stride-2 layer is a
+        stride-2 layer with the two widths swapped, so BOTH widths of a layer have to be input widths some kernel form takes: a
+        multiple of 64 for the position-major (4^3 <-> 2^3) and whole-sample (8^3 <-> 4^3) forms, 64 * 2^k (float32: 32 * 2^k) for the
+        implicit GEMM every other shape falls back to.  The engines ask less of an OUTPUT width (a multiple of 8: the 4^3 -> 2^3
+        form admits 136), which is why such a model evaluates and cannot be fitted."""
+        bk, vec, name = (64, 8, 'bf16') if self.dt == L.VV_BF16 else (32, 4, 'f32')
+        for var, what, direction, side, cin, cout in self._stride2_launches():
+            if self._route(direction, side, cin, cout) == 'igemm' and not R.igemm_admits(cin, cout, self.dt):
+                raise ValueError("%s cannot be fitted in '%s': its %s is a stride-2 %s %d^3 x %d -> %d channels, and no kernel form takes "
+                                 "it.  Width rule: input channels a multiple of 64 at 4^3 <-> 2^3 and 8^3 <-> 4^3 (position-major / whole-sample "
+                                 "forms), %d * 2^k elsewhere (implicit GEMM); output channels a multiple of %d; a layer's data gradient swaps "
+                                 "its two widths, so both must be input widths"
+                                 % (var, name, what, 'convolution' if direction == R.CONV else 'transposed convolution', side, cin, cout, bk, vec))
 
     def _begin(self, *engines, step=False):
         """Start of every entry point: the switches are read once, the engines packed without folded vectors (batch statistics); an
@@ -759,15 +792,21 @@ class Trainer:
         L.call('vv_pack_conv_k4', L.ptr(w5), L.ptr(w5p), 1, cl, dt, st)
         dh = self._aempty(B, side, side, side, cl)
         L.call('vv_conv3d_first_fwd', L.ptr(dlogit), L.ptr(w5p), None, None, L.ptr(dh), B, D, cl, 0, dt, st)
+        keep = self.debug is not None                        # tests: the activation gradients of every layer, by layer index
+        dhs, dcvs = ([None] * nd, [None] * nd) if keep else (None, None)
         for i in range(nd - 1, 0, -1):                       # stride-2 transposed convs
             cin, cout = fd[i - 1], fd[i]
             dcv = self._bn_bwd(dc_[i], dh, dbn[i], B * side ** 3, 'dec/bnT%d/gamma' % i, 'dec/bnT%d/beta' % i, act)
+            if keep:
+                dhs[i], dcvs[i] = dh, dcv
             wk = dec.params['convT%d/kernel' % i]            # Keras [4,4,4,cout,cin]
             self._wgrad_conv(dcv, dh_[i - 1], self._g('dec/convT%d/kernel' % i), B, side, cout, cin, ready='dec/convT%d/kernel' % i)
             dh = self._conv(dcv, wk, B, side, cout, cin)     # read as a forward conv kernel [4,4,4,Cin_c=cout,Cout_c=cin]
             side //= 2
         # D1 (dense panel over the S^3 seed)
         dcv = self._bn_bwd(c_d1, dh, bn_d1, B * S ** 3, 'dec/bnT0/gamma', 'dec/bnT0/beta', act)
+        if keep:
+            dhs[0], dcvs[0] = dh, dcv
         dpanel = self._empty(n1, lin)
         self._wgrad_dense(dcv, t0, dpanel, B, n1, lin)
         L.call('vv_unpack_convT_dense_grad', L.ptr(dpanel), L.ptr(self._g('dec/convT0/kernel')), S, ch, fd[0], st)
@@ -790,8 +829,9 @@ class Trainer:
         else:
             de = dz if drop_mask is None else self._mask_scale(dz, drop_mask, drop_scale, B)
         if self.debug is not None:
-            self.debug.update({'dlogit': dlogit, 'probs': probs, 'enc_out': enc_out, 'z': z, 'dz': dz, 'de': de, 'c_d0': c_d0, 'dcv0': dcv0,
-                               't0': t0, 'dt0': dt0, 'h_dec': dh_, 'c_dec': dc_})
+            self.debug.update({'dlogit': dlogit, 'probs': probs, 'enc_out': enc_out, 'z': z, 'z_act': z_act, 'dz': dz, 'de': de, 'c_d0': c_d0,
+                               'dcv0': dcv0, 't0': t0, 'dt0': dt0, 'h_dec': dh_, 'c_dec': dc_, 'dh_dec': dhs, 'dcv_dec': dcvs,
+                               'bn_d0': bn_d0, 'bn_dec': dbn, 'dpanel_dec': dpanel})
         return de
 
     def _encoder_backward(self, x, de, est, B):
@@ -809,17 +849,22 @@ class Trainer:
         L.call('vv_pack_conv_k4s1_meanpool', L.ptr(enc.params['conv%d/kernel' % ne]), L.ptr(wef), Sside_e, fe[ne - 1], E_out, L.VV_F32, st)
         dh = self._dense(self._cast(de), self._transposed_panel(wef, E_out, K5), B, K5, E_out)
         side = Sside_e
+        keep = self.debug is not None                        # tests: the activation gradients of every layer, by layer index
+        dhs, dcvs = ([None] * ne, [None] * ne) if keep else (None, None)
         for i in range(ne - 1, 0, -1):                       # stride-2 convs
             cin, cout = fe[i - 1], fe[i]
             dcv = self._bn_bwd(ec[i], dh, ebn[i], B * side ** 3, 'enc/bn%d/gamma' % i, 'enc/bn%d/beta' % i, act)
+            if keep:
+                dhs[i], dcvs[i] = dh, dcv
             wk = enc.params['conv%d/kernel' % i]             # Keras [4,4,4,cin,cout]
             self._wgrad_conv(eh[i - 1], dcv, self._g('enc/conv%d/kernel' % i), B, 2 * side, cin, cout, ready='enc/conv%d/kernel' % i)
             dh = self._convT(dcv, wk, B, side, cout, cin)    # read as a transposed kernel [4,4,4,Cout_T=cin,Cin_T=cout]
             side *= 2
         dcv = self._bn_bwd(ec[0], dh, ebn[0], B * side ** 3, 'enc/bn0/gamma', 'enc/bn0/beta', act)
         self._wgrad_conv(x, dcv, self._g('enc/conv0/kernel'), B, D, 1, fe[0], ready='enc/conv0/kernel')
-        if self.debug is not None:
-            self.debug.update({'h_enc': eh, 'c_enc': ec})
+        if keep:
+            dhs[0], dcvs[0] = dh, dcv
+            self.debug.update({'h_enc': eh, 'c_enc': ec, 'dh_enc': dhs, 'dcv_enc': dcvs, 'bn_enc': ebn, 'dpanel_enc': dpanel})
 
     def _apply(self):
         # ---------------- cross-rank gradient sum, then Adam on every replica

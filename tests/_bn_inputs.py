@@ -23,8 +23,9 @@ EPS, MOMENTUM = 1e-3, 0.99
 V = {'f32': 4, 'bf16': 8}                       # channels per thread (BnVec<T>::V)
 
 # C / V: 96, 65, 86, 255 are in 64..256 and no power of two (bn_shape_ok admits them: `channels / V >= 64`), rows_par = 256 / (C / V) =
-# 2, 3, 2, 1 with 64, 61, 84, 1 threads of the workgroup owning no row; 32 is the power of two next to them (rows_par = 8)
-BN_CV = (96, 65, 86, 255, 32)
+# 2, 3, 2, 1 with 64, 61, 84, 1 threads of the workgroup owning no row; 32 is the power of two next to them (rows_par = 8); 24 is below 64
+# and no divisor of 256 (192 bf16 / 96 float32 channels: rows_par = 10, 16 threads without a row), a width bn_shape_ok once refused
+BN_CV = (96, 65, 86, 255, 32, 24)
 BN_BIG = (300000, 64)                           # rows past 1024 * 128 (f32) / 1024 * 256 (bf16) reduction rows: bn_blocks' cap, and past
 #                                                 4096 * 32 / 4096 * 64 sweep rows: bn_sweep_blocks' cap -- every block walks more than two trips
 

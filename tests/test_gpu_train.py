@@ -32,10 +32,18 @@ def _rel(a, b):
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
 
 
-@pytest.mark.parametrize('D,Lz,var,B', [(32, 64, True, 4), (16, 64, True, 6), (32, 64, False, 3)])
+# (64, ...): the reference's native grid (train_modelnet_category_VAE.py: make_config(latent_dim, 64, True)), B = 2
+@pytest.mark.parametrize('D,Lz,var,B', [(32, 64, True, 4), (16, 64, True, 6), (32, 64, False, 3), (64, 64, True, 2), (64, 64, False, 2)])
 def test_fit_step_matches_autograd_oracle(D, Lz, var, B):
-    from oracle import torch_oracle as to
     cfg, ep, dp, model, x, eps = _setup(D, Lz, var, B)
+    _assert_fit_step_matches_oracle(cfg, ep, dp, model, x, eps, var, 'D%d L%d var%d B%d' % (D, Lz, var, B))
+
+
+def _assert_fit_step_matches_oracle(cfg, ep, dp, model, x, eps, var, label):
+    """One f32 fit of `model` (weights ep / dp) on (x, eps) against the float64 autograd oracle: losses, every gradient, the Adam step
+    and the moving statistics.  Shared with tests/test_gpu_train_native.py (other depths)."""
+    from oracle import torch_oracle as to
+    B = x.shape[0]
     ref = to.fit_step(cfg, ep, dp, x, x, eps, lr=1e-3, variational=var)
     model._train_helper().debug = {}                     # keep the step's intermediates (d loss / d pre-BN dense output below)
     out = model.fit((x, x), _eps=eps) if var else model.fit((x, x))
@@ -76,7 +84,7 @@ def test_fit_step_matches_autograd_oracle(D, Lz, var, B):
                 continue
             big = np.abs(g) > 1e-3 * np.abs(g).max()
             assert np.abs(step_got - step_ref)[big].max() <= 0.02 * 1e-3 + 1e-9, key
-    print('\n[fit D%d L%d var%d B%d] worst grad rel err %.2e (%s)' % (D, Lz, var, B, max(worst.values()), max(worst, key=worst.get)))
+    print('\n[fit %s] worst grad rel err %.2e (%s)' % (label, max(worst.values()), max(worst, key=worst.get)))
 
 
 def test_two_steps_loss_decreases_and_state_advances():
@@ -110,11 +118,14 @@ def test_weight_gradient_stream_is_bit_identical(dtype, monkeypatch):
             assert torch.equal(a[k], b[k]), k
 
 
-def test_decoder_only_step_matches_full_step():
+@pytest.mark.parametrize('D,B,dtype', [(32, 4, 'f32'), (64, 2, 'f32'), (64, 2, 'bf16')])
+def test_decoder_only_step_matches_full_step(D, B, dtype):
     """Trainer.step_from_latent (image -> 3D model, nolbo.py:786-833) is the decoder + latent part of the full step: fed
-    the full step's encoder output it must produce the same decoder gradients and the same d loss / d enc_out."""
+    the full step's encoder output it must produce the same decoder gradients and the same d loss / d enc_out.  At 64^3 the
+    decoder runs its native forms (S = 4 dense panels, skip / igemm / direct layers, the side-64 final layer); in bf16 the two
+    trainers batch different weight-image lists (Trainer._prepack) and must still agree bit for bit."""
     from voxvae import train as T
-    cfg, ep, dp, model, x, eps = _setup(32, 64, True, 4)
+    cfg, ep, dp, model, x, eps = _setup(D, 64, True, B, dtype=dtype)
     xd = torch.from_numpy(x).to(DEV)
     epsd = torch.from_numpy(eps).to(DEV)
     full = T.Trainer(model._enc_eng, model._dec_eng, True, 1e-3)

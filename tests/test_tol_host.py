@@ -388,10 +388,11 @@ def test_bn_inputs_are_what_they_claim(rows, C):
 
 def test_bn_case_table_reaches_what_it_names():
     cvs = {(dt, C // BI.V[dt]) for dt, rows, C in BI.BN_SHAPES}
-    assert {cv for _, cv in cvs} == set(BI.BN_CV) and {BI.rows_par(cv) for cv in BI.BN_CV} == {1, 2, 3, 8}
+    assert {cv for _, cv in cvs} == set(BI.BN_CV) and {BI.rows_par(cv) for cv in BI.BN_CV} == {1, 2, 3, 8, 10}
+    assert any(cv < 64 and 256 % cv for cv in BI.BN_CV)                                      # idle threads below 64 vectors too
     for dt, rows, C in BI.BN_STATS_CASES:                                                    # bn_shape_ok
         cv = C // BI.V[dt]
-        assert C % BI.V[dt] == 0 and cv <= 256 and (cv >= 64 or 256 % cv == 0)
+        assert C % BI.V[dt] == 0 and cv <= 256
     for cv in BI.BN_CV:
         rp = BI.rows_par(cv)
         assert {1, 4 * rp - 1, 4 * rp + 1, 777} <= set(BI.bn_rows(cv)) and (rp == 1 or min(BI.bn_rows(cv)) < rp)     # fewer rows than run in parallel
