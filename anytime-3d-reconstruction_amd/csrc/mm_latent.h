@@ -7,48 +7,21 @@
 // The head output of one sample is [mean_c (Lc) | logVar_c (Lc) | mean_i (Li) | logVar_i (Li)]; every latent-shaped array
 // (z, eps, noise, dz_in) is [category (Lc) | instance (Li)].
 //
-// Same bits on both sides.  Everything below is float32 +, -, *, the correctly rounded division and square root, comparisons and bit
-// operations, with floating-point contraction switched OFF in every function; exp is detect_decode.h's vv_det_exp (no libm / ocml
-// transcendental).  Every sum runs in one fixed order: over a latent's elements, over the prototypes' rows and over the classes in
-// index order; over the batch (the regulariser's pairs) as VV_MM_THREADS strided partial sums -- partial t takes j = t, t + 256, ... in
+// Same bits on both sides.  The arithmetic of one latent element is latent_elem.h's, shared with prior_latent.h; what is added here
+// keeps its rules: float32 +, -, *, the correctly rounded division and square root, comparisons and bit operations, with floating-point
+// contraction switched OFF in every function, exp from detect_decode.h.  Every sum runs in one fixed order: over a latent's elements,
+// over the prototypes' rows and over the classes in index order; over the batch (the regulariser's pairs) as VV_MM_THREADS strided partial sums -- partial t takes j = t, t + 256, ... in
 // ascending order -- that are then added in index order; the backward's pair sums in ascending j.
 //
 // No inline assembly, no atomics, no memory besides the arguments.
 #pragma once
-#include "detect_decode.h"
+#include "latent_elem.h"
 
-#define VV_MM_HD VV_DET_HD
+#define VV_MM_HD VV_LE_HD
 
 constexpr int VV_MM_MAX_L = 64;          // width of one latent group
 constexpr int VV_MM_MAX_C = 256;         // categories, instances per category
 constexpr int VV_MM_THREADS = 256;       // the workgroup, and the number of strided partial sums over the batch
-constexpr int VV_MM_F32 = 0, VV_MM_BF16 = 1;   // = VV_F32, VV_BF16 of include/voxvae.h
-
-VV_MM_HD float vv_mm_inf() { return vv_det_float(0x7F800000u); }
-VV_MM_HD float vv_mm_abs(float x) { return vv_det_float(vv_det_bits(x) & 0x7FFFFFFFu); }
-// tf.clip_by_value(x, -10, 10); a NaN stays
-VV_MM_HD float vv_mm_clip(float x) { return x != x ? x : (x < -10.0f ? -10.0f : (x > 10.0f ? 10.0f : x)); }
-// where the clip lets a gradient through: the rule of vv_reparam_kl_bwd
-VV_MM_HD bool vv_mm_clip_passes(float raw) { return raw >= -10.0f && raw <= 10.0f; }
-VV_MM_HD float vv_mm_std(float lv) { return __builtin_sqrtf(vv_det_exp(lv)); }
-// sampling(mu, logVar) with the draw injected (function.py:35-38)
-VV_MM_HD float vv_mm_sample(float mean, float lv, float eps) {
-#pragma clang fp contract(off)
-    const float s = vv_mm_std(lv);
-    const float t = s * eps;
-    return mean + t;
-}
-// float32 -> bfloat16, round to nearest even; a NaN keeps its sign and becomes quiet
-VV_MM_HD unsigned short vv_mm_bf16(float x) {
-    const unsigned u = vv_det_bits(x);
-    if (x != x) return (unsigned short)((u >> 16) | 0x40u);
-    return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-VV_MM_HD void vv_mm_store_act(void *p, int dtype, long long i, float v) {
-    if (!p) return;
-    if (dtype == VV_MM_BF16) static_cast<unsigned short *>(p)[i] = vv_mm_bf16(v);
-    else static_cast<float *>(p)[i] = v;
-}
 
 // ------------------------------------------------------------------------------------------------ evaluation (nolbo.py:183-252)
 struct VvMmEval {
@@ -66,7 +39,7 @@ VV_MM_HD float vv_mm_z(const float *enc_out, const float *eps, int Lc, int Li, i
     const float *row = enc_out + (long long)b * (2 * Lc + 2 * Li);
     const float mean = e < Lc ? row[e] : row[2 * Lc + (e - Lc)];
     const float raw = e < Lc ? row[Lc + e] : row[2 * Lc + Li + (e - Lc)];
-    return vv_mm_sample(mean, vv_mm_clip(raw), eps[(long long)b * (Lc + Li) + e]);
+    return vv_le_sample(mean, vv_le_clip(raw), eps[(long long)b * (Lc + Li) + e]);
 }
 // tf.reduce_mean(mean_category_prior, axis=0)[j] (:200)
 VV_MM_HD float vv_mm_colmean(const float *prior_cat, int C, int Lc, int j) {
@@ -81,29 +54,6 @@ VV_MM_HD float vv_mm_fill(float z, float m, float colmean) {
     const float v = z * m;
     return v == 0.0f ? colmean : v;
 }
-// sum_j [mask_j *] (z_j - p_j)^2 in index order (:218, :239)
-VV_MM_HD float vv_mm_dist(const float *z, const float *mask, const float *p, int L) {
-#pragma clang fp contract(off)
-    float d = 0.0f;
-    for (int j = 0; j < L; ++j) {
-        const float t = z[j] - p[j];
-        const float q = t * t;
-        d = d + (mask ? mask[j] * q : q);
-    }
-    return d;
-}
-// first argmin among the distances below +inf; none -> 0 (the contract of vv_nearest_category).  (d, c) pairs are totally ordered, so
-// the running minimum does not depend on the order in which candidates or partial results are merged.
-struct VvMmBest {
-    float d;
-    int c;
-};
-VV_MM_HD VvMmBest vv_mm_best_init() { return VvMmBest{vv_mm_inf(), 0x7FFFFFFF}; }
-VV_MM_HD void vv_mm_best_take(VvMmBest &s, float d, int c) {
-    if (!(d < vv_mm_inf())) return;
-    if (d < s.d || (d == s.d && c < s.c)) s.d = d, s.c = c;
-}
-VV_MM_HD int vv_mm_best_index(const VvMmBest &s) { return s.d < vv_mm_inf() ? s.c : 0; }
 // where(mask == 0, prior[idx] + eps2, z) (:242-243; sqrt(exp(0)) = 1 exactly)
 VV_MM_HD float vv_mm_correct(float m, float prior, float eps2, float z) {
 #pragma clang fp contract(off)
@@ -135,24 +85,24 @@ VV_MM_HD void vv_mm_eval_sample(const VvMmEval &a, int b) {
         for (int j = 0; j < Lc; ++j) z[j] = vv_mm_fill(z[j], m[j], vv_mm_colmean(a.prior_cat, a.C, Lc, j));
     for (int e = 0; e < L; ++e) {
         a.z[(long long)b * L + e] = z[e];
-        vv_mm_store_act(a.z_act, a.act_dtype, (long long)b * L + e, z[e]);
+        vv_le_store_act(a.z_act, a.act_dtype, (long long)b * L + e, z[e]);
     }
-    VvMmBest cat = vv_mm_best_init(), inst = vv_mm_best_init(), msk = vv_mm_best_init(), cor = vv_mm_best_init();
-    for (int c = 0; c < a.C; ++c) vv_mm_best_take(cat, vv_mm_dist(z, nullptr, a.prior_cat + (long long)c * Lc, Lc), c);
-    for (int c = 0; c < a.I; ++c) vv_mm_best_take(inst, vv_mm_dist(z + Lc, nullptr, a.prior_inst + ((long long)b * a.I + c) * Li, Li), c);
+    VvLeBest cat = vv_le_best_init(), inst = vv_le_best_init(), msk = vv_le_best_init(), cor = vv_le_best_init();
+    for (int c = 0; c < a.C; ++c) vv_le_best_take(cat, vv_le_dist(z, nullptr, a.prior_cat + (long long)c * Lc, Lc), c);
+    for (int c = 0; c < a.I; ++c) vv_le_best_take(inst, vv_le_dist(z + Lc, nullptr, a.prior_inst + ((long long)b * a.I + c) * Li, Li), c);
     int *ix = a.idx + (long long)b * 4;
-    ix[0] = vv_mm_best_index(cat), ix[1] = vv_mm_best_index(inst), ix[2] = ix[0], ix[3] = ix[0];
+    ix[0] = vv_le_best_index(cat), ix[1] = vv_le_best_index(inst), ix[2] = ix[0], ix[3] = ix[0];
     if (!m) return;
-    for (int c = 0; c < a.C; ++c) vv_mm_best_take(msk, vv_mm_dist(z, m, a.prior_cat + (long long)c * Lc, Lc), c);
-    ix[2] = vv_mm_best_index(msk);
+    for (int c = 0; c < a.C; ++c) vv_le_best_take(msk, vv_le_dist(z, m, a.prior_cat + (long long)c * Lc, Lc), c);
+    ix[2] = vv_le_best_index(msk);
     for (int j = 0; j < Lc; ++j) corr[j] = vv_mm_correct(m[j], a.prior_cat[(long long)ix[2] * Lc + j], a.eps2[(long long)b * Lc + j], z[j]);
     for (int e = 0; e < L; ++e) {
         const float v = e < Lc ? corr[e] : z[e];
         a.z_corr[(long long)b * L + e] = v;
-        vv_mm_store_act(a.z_corr_act, a.act_dtype, (long long)b * L + e, v);
+        vv_le_store_act(a.z_corr_act, a.act_dtype, (long long)b * L + e, v);
     }
-    for (int c = 0; c < a.C; ++c) vv_mm_best_take(cor, vv_mm_dist(corr, nullptr, a.prior_cat + (long long)c * Lc, Lc), c);
-    ix[3] = vv_mm_best_index(cor);
+    for (int c = 0; c < a.C; ++c) vv_le_best_take(cor, vv_le_dist(corr, nullptr, a.prior_cat + (long long)c * Lc, Lc), c);
+    ix[3] = vv_le_best_index(cor);
 }
 VV_MM_HD void vv_mm_eval_all(const VvMmEval &a) {
     for (int b = 0; b < a.B; ++b) vv_mm_eval_sample(a, b);
@@ -177,15 +127,11 @@ struct VvMmTrain {
     int B, Lc, Li, C;
 };
 // what element e of sample b reads
-struct VvMmElem {
-    float mean, raw, lv, eps, mt, lvt, eps_p, dz;
-    bool from_prior;
-};
-VV_MM_HD VvMmElem vv_mm_elem(const VvMmTrain &a, int b, int e) {
+VV_MM_HD VvLeElem vv_mm_elem(const VvMmTrain &a, int b, int e) {
     const int Lc = a.Lc, Li = a.Li;
     const float *row = a.enc_out + (long long)b * (2 * Lc + 2 * Li);
     const long long le = (long long)b * (Lc + Li) + e;
-    VvMmElem v;
+    VvLeElem v;
     if (e < Lc) {
         v.mean = row[e], v.raw = row[Lc + e];
         v.mt = a.mean_cp[(long long)b * Lc + e], v.lvt = a.lv_cp[(long long)b * Lc + e];
@@ -193,43 +139,24 @@ VV_MM_HD VvMmElem vv_mm_elem(const VvMmTrain &a, int b, int e) {
         v.mean = row[2 * Lc + (e - Lc)], v.raw = row[2 * Lc + Li + (e - Lc)];
         v.mt = a.mean_ip[(long long)b * Li + (e - Lc)], v.lvt = a.lv_ip[(long long)b * Li + (e - Lc)];
     }
-    v.lv = vv_mm_clip(v.raw);
+    v.lv = vv_le_clip(v.raw);
     v.eps = a.eps[le], v.eps_p = a.eps_p[le];
     v.from_prior = a.noise ? !(a.noise[le] == 0.0f) : false;          // tf.where(noise == 0, z, z_prior) (:123)
     v.dz = a.dz_in ? a.dz_in[le] : 0.0f;
     return v;
 }
-VV_MM_HD float vv_mm_z_in(const VvMmElem &v) { return v.from_prior ? vv_mm_sample(v.mt, v.lvt, v.eps_p) : vv_mm_sample(v.mean, v.lv, v.eps); }
-// one element of kl_loss's sum (function.py:96)
-VV_MM_HD float vv_mm_kl_term(const VvMmElem &v) {
-#pragma clang fp contract(off)
-    const float a = 0.5f * (v.lvt - v.lv);
-    const float d = v.mean - v.mt;
-    const float num = vv_det_exp(v.lv) + d * d;
-    const float den = 2.0f * vv_det_exp(v.lvt);
-    return (a + num / den) - 0.5f;
-}
 // sum_l |m_i - m_j| / exp(0.5 lv_i) in index order (function.py:49-50): the scale is row i's
 VV_MM_HD float vv_mm_pair_dist(const float *mi, const float *mj, const float *lvi, int L) {
 #pragma clang fp contract(off)
     float d = 0.0f;
-    for (int l = 0; l < L; ++l) d = d + vv_mm_abs(mi[l] - mj[l]) / vv_det_exp(0.5f * lvi[l]);
+    for (int l = 0; l < L; ++l) d = d + vv_le_abs(mi[l] - mj[l]) / vv_le_scale(lvi[l]);
     return d;
-}
-// where(x > 0, 0, x^2) (function.py:53-54) and its derivative
-VV_MM_HD float vv_mm_hinge(float x) {
-#pragma clang fp contract(off)
-    return x > 0.0f ? 0.0f : x * x;
-}
-VV_MM_HD float vv_mm_hinge_grad(float x) {
-#pragma clang fp contract(off)
-    return x > 0.0f ? 0.0f : 2.0f * x;
 }
 // 1 where the two one-hot rows are equal, else 0 (function.py:58-66)
 VV_MM_HD float vv_mm_same_class(const float *cls, int C, int i, int j) {
 #pragma clang fp contract(off)
     float cd = 0.0f;
-    for (int c = 0; c < C; ++c) cd = cd + vv_mm_abs(cls[(long long)i * C + c] - cls[(long long)j * C + c]);
+    for (int c = 0; c < C; ++c) cd = cd + vv_le_abs(cls[(long long)i * C + c] - cls[(long long)j * C + c]);
     return cd > 0.0f ? 0.0f : 1.0f;
 }
 VV_MM_HD float vv_mm_dist_in_z(int L) { return (float)(3 * L); }
@@ -241,15 +168,9 @@ VV_MM_HD void vv_mm_reg_partial(const VvMmTrain &a, int i, int t, float &pc, flo
     for (int j = t; j < a.B; j += VV_MM_THREADS) {
         const float dc = vv_mm_pair_dist(a.mean_cp + (long long)i * Lc, a.mean_cp + (long long)j * Lc, a.lv_cp + (long long)i * Lc, Lc);
         const float di = vv_mm_pair_dist(a.mean_ip + (long long)i * Li, a.mean_ip + (long long)j * Li, a.lv_ip + (long long)i * Li, Li);
-        pc = pc + vv_mm_hinge(dc - vv_mm_dist_in_z(Lc));
-        pi = pi + vv_mm_hinge(di - vv_mm_dist_in_z(Li)) * vv_mm_same_class(a.cat_onehot, a.C, i, j);
+        pc = pc + vv_le_hinge(dc - vv_mm_dist_in_z(Lc));
+        pi = pi + vv_le_hinge(di - vv_mm_dist_in_z(Li)) * vv_mm_same_class(a.cat_onehot, a.C, i, j);
     }
-}
-VV_MM_HD float vv_mm_sum(const float *v, int n) {
-#pragma clang fp contract(off)
-    float s = 0.0f;
-    for (int k = 0; k < n; ++k) s = s + v[k];
-    return s;
 }
 VV_MM_HD int vv_mm_partials(int B) { return B < VV_MM_THREADS ? B : VV_MM_THREADS; }
 
@@ -258,16 +179,16 @@ VV_MM_HD void vv_mm_train_fwd_sample(const VvMmTrain &a, int i) {
     const int Lc = a.Lc, Li = a.Li, L = Lc + Li;
     float term[2 * VV_MM_MAX_L], pc[VV_MM_THREADS], pi[VV_MM_THREADS];
     for (int e = 0; e < L; ++e) {
-        const VvMmElem v = vv_mm_elem(a, i, e);
-        const float zi = vv_mm_z_in(v);
+        const VvLeElem v = vv_mm_elem(a, i, e);
+        const float zi = vv_le_z_in(v);
         a.z_in[(long long)i * L + e] = zi;
-        vv_mm_store_act(a.z_in_act, a.act_dtype, (long long)i * L + e, zi);
-        term[e] = vv_mm_kl_term(v);
+        vv_le_store_act(a.z_in_act, a.act_dtype, (long long)i * L + e, zi);
+        term[e] = vv_le_kl_term(v);
     }
-    a.kl[i] = vv_mm_sum(term, Lc) + vv_mm_sum(term + Lc, Li);
+    a.kl[i] = vv_le_sum(term, Lc) + vv_le_sum(term + Lc, Li);
     const int n = vv_mm_partials(a.B);
     for (int t = 0; t < n; ++t) vv_mm_reg_partial(a, i, t, pc[t], pi[t]);
-    a.reg[i] = vv_mm_sum(pc, n) + vv_mm_sum(pi, n);
+    a.reg[i] = vv_le_sum(pc, n) + vv_le_sum(pi, n);
 }
 
 // ---- backward of total = mean_b kl + mean_b reg + shape, with dz_in = d shape / d z_in.
@@ -279,48 +200,22 @@ VV_MM_HD void vv_mm_pair_grads(const VvMmTrain &a, int grp, int i, int j, float 
     const float same = grp ? vv_mm_same_class(a.cat_onehot, a.C, i, j) : 1.0f;
     const float dij = vv_mm_pair_dist(m + (long long)i * L, m + (long long)j * L, lv + (long long)i * L, L);
     const float dji = vv_mm_pair_dist(m + (long long)j * L, m + (long long)i * L, lv + (long long)j * L, L);
-    gij = same == 0.0f ? 0.0f : vv_mm_hinge_grad(dij - vv_mm_dist_in_z(L));
-    gji = same == 0.0f ? 0.0f : vv_mm_hinge_grad(dji - vv_mm_dist_in_z(L));
+    gij = same == 0.0f ? 0.0f : vv_le_hinge_grad(dij - vv_mm_dist_in_z(L));
+    gji = same == 0.0f ? 0.0f : vv_le_hinge_grad(dji - vv_mm_dist_in_z(L));
 }
-// pair (i, j)'s share of d reg / d mean_i[l] and d reg / d lv_i[l]; the derivative of |x| at 0 is 0
-VV_MM_HD void vv_mm_pair_accumulate(float &am, float &alv, float gij, float gji, float mi, float mj, float ei, float lvj) {
-#pragma clang fp contract(off)
-    const float diff = mi - mj;
-    if (diff == 0.0f) return;                       // sign 0: nothing reaches the means, and |diff| = 0 nothing the scale
-    const float sgn = diff > 0.0f ? 1.0f : (diff < 0.0f ? -1.0f : diff);      // a NaN stays
-    const float ej = vv_det_exp(0.5f * lvj);
-    am = am + (gij * sgn) / ei;
-    am = am + (gji * sgn) / ej;
-    alv = alv + (gij * -0.5f) * (vv_mm_abs(diff) / ei);
-}
-// element e of sample i, given the accumulated regulariser sums: the four outputs
+// element e of sample i, given the accumulated regulariser sums: the four outputs, stored by this stage's layout
 VV_MM_HD void vv_mm_bwd_store(const VvMmTrain &a, int i, int e, float am, float alv) {
-#pragma clang fp contract(off)
     const int Lc = a.Lc, Li = a.Li;
-    const VvMmElem v = vv_mm_elem(a, i, e);
-    const float ex = vv_det_exp(v.lv), et = vv_det_exp(v.lvt), d = v.mean - v.mt;
-    const float kl_mean = d / et;                                              // d kl / d mean; the prior mean gets the negative
-    const float kl_lv = ex / (2.0f * et) - 0.5f;
-    const float kl_lvt = 0.5f - (ex + d * d) / (2.0f * et);
-    float g_mean = kl_mean * a.inv_batch, g_lv = kl_lv * a.inv_batch;
-    float g_mt = (am - kl_mean) * a.inv_batch, g_lvt = (kl_lvt + alv) * a.inv_batch;
-    if (v.from_prior) {
-        g_mt = g_mt + v.dz;
-        g_lvt = g_lvt + v.dz * ((0.5f * vv_mm_std(v.lvt)) * v.eps_p);
-    } else {
-        g_mean = g_mean + v.dz;
-        g_lv = g_lv + v.dz * ((0.5f * vv_mm_std(v.lv)) * v.eps);
-    }
-    if (!vv_mm_clip_passes(v.raw)) g_lv = 0.0f;
+    const VvLeGrads g = vv_le_elem_grads(vv_mm_elem(a, i, e), am, alv, 1.0f, a.inv_batch);
     float *row = a.d_enc_out + (long long)i * (2 * Lc + 2 * Li);
     if (e < Lc) {
-        row[e] = g_mean, row[Lc + e] = g_lv;
-        if (a.d_mean_cp) a.d_mean_cp[(long long)i * Lc + e] = g_mt;
-        if (a.d_lv_cp) a.d_lv_cp[(long long)i * Lc + e] = g_lvt;
+        row[e] = g.mean, row[Lc + e] = g.lv;
+        if (a.d_mean_cp) a.d_mean_cp[(long long)i * Lc + e] = g.mt;
+        if (a.d_lv_cp) a.d_lv_cp[(long long)i * Lc + e] = g.lvt;
     } else {
-        row[2 * Lc + (e - Lc)] = g_mean, row[2 * Lc + Li + (e - Lc)] = g_lv;
-        if (a.d_mean_ip) a.d_mean_ip[(long long)i * Li + (e - Lc)] = g_mt;
-        if (a.d_lv_ip) a.d_lv_ip[(long long)i * Li + (e - Lc)] = g_lvt;
+        row[2 * Lc + (e - Lc)] = g.mean, row[2 * Lc + Li + (e - Lc)] = g.lv;
+        if (a.d_mean_ip) a.d_mean_ip[(long long)i * Li + (e - Lc)] = g.mt;
+        if (a.d_lv_ip) a.d_lv_ip[(long long)i * Li + (e - Lc)] = g.lvt;
     }
 }
 // element e's prior mean and log-variance of sample j
@@ -342,10 +237,10 @@ VV_MM_HD void vv_mm_train_bwd_sample(const VvMmTrain &a, int i) {
             const int grp = e < Lc ? 0 : 1;
             float mi, lvi, mj, lvj;
             vv_mm_prior_at(a, i, e, mi, lvi);
-            const float ei = vv_det_exp(0.5f * lvi);
+            const float ei = vv_le_scale(lvi);
             for (int t = 0; t < n; ++t) {
                 vv_mm_prior_at(a, j0 + t, e, mj, lvj);
-                vv_mm_pair_accumulate(am[e], alv[e], g[2 * grp][t], g[2 * grp + 1][t], mi, mj, ei, lvj);
+                vv_le_pair_accumulate(am[e], alv[e], g[2 * grp][t], g[2 * grp + 1][t], mi, mj, ei, vv_le_scale(lvj));
             }
         }
     }

@@ -13,33 +13,17 @@
 //               index order.  Backward: in pieces of 256 samples j, thread t computes the four pair weights of (i, j0 + t); then thread
 //               e accumulates element e's sums over the piece in ascending j.
 // No atomics, no inline assembly: a given input gives the same bits on every run, and the bits of the host entries.  gfx950 only.
-#include "common.h"
+#include "latent_block.h"
 #include "mm_latent.h"
 
 namespace {
 
-static_assert(VV_MM_F32 == VV_F32 && VV_MM_BF16 == VV_BF16, "activation dtype codes");
-
-// The workgroup's minimum of (d, c) pairs in the order of vv_mm_best_take; every thread gets the index.  red: [4] pairs of LDS.
-__device__ __forceinline__ int mm_block_argmin(VvMmBest s, VvMmBest *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float od = __shfl_xor(s.d, o, 64);
-        const int oc = __shfl_xor(s.c, o, 64);
-        vv_mm_best_take(s, od, oc);
-    }
-    __syncthreads();                                   // the previous round's readers are done with red
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    VvMmBest r = vv_mm_best_init();
-#pragma unroll
-    for (int w = 0; w < VV_MM_THREADS / 64; ++w) vv_mm_best_take(r, red[w].d, red[w].c);
-    return vv_mm_best_index(r);
-}
+static_assert(VV_LE_F32 == VV_F32 && VV_LE_BF16 == VV_BF16, "activation dtype codes");
+static_assert(VV_MM_THREADS == 64 * VV_LE_WAVES, "the workgroup of vv_le_block_argmin");
 
 __global__ __launch_bounds__(VV_MM_THREADS) void mm_eval_kernel(const VvMmEval a) {
     __shared__ float z[2 * VV_MM_MAX_L], corr[VV_MM_MAX_L], msk[VV_MM_MAX_L];
-    __shared__ VvMmBest red[VV_MM_THREADS / 64];
+    __shared__ VvLeBest red[VV_LE_WAVES];
     const int t = threadIdx.x, b = blockIdx.x, Lc = a.Lc, Li = a.Li, L = Lc + Li;
     const bool masked = a.mask != nullptr;
     if (t < L) {
@@ -51,26 +35,26 @@ __global__ __launch_bounds__(VV_MM_THREADS) void mm_eval_kernel(const VvMmEval a
         }
         z[t] = v;
         a.z[(long long)b * L + t] = v;
-        vv_mm_store_act(a.z_act, a.act_dtype, (long long)b * L + t, v);
+        vv_le_store_act(a.z_act, a.act_dtype, (long long)b * L + t, v);
     }
     __syncthreads();
-    VvMmBest cat = vv_mm_best_init(), inst = vv_mm_best_init(), mk = vv_mm_best_init(), cor = vv_mm_best_init();
-    if (t < a.C) vv_mm_best_take(cat, vv_mm_dist(z, nullptr, a.prior_cat + (long long)t * Lc, Lc), t);
-    if (t < a.I) vv_mm_best_take(inst, vv_mm_dist(z + Lc, nullptr, a.prior_inst + ((long long)b * a.I + t) * Li, Li), t);
-    if (masked && t < a.C) vv_mm_best_take(mk, vv_mm_dist(z, msk, a.prior_cat + (long long)t * Lc, Lc), t);
-    const int i0 = mm_block_argmin(cat, red), i1 = mm_block_argmin(inst, red);
+    VvLeBest cat = vv_le_best_init(), inst = vv_le_best_init(), mk = vv_le_best_init(), cor = vv_le_best_init();
+    if (t < a.C) vv_le_best_take(cat, vv_le_dist(z, nullptr, a.prior_cat + (long long)t * Lc, Lc), t);
+    if (t < a.I) vv_le_best_take(inst, vv_le_dist(z + Lc, nullptr, a.prior_inst + ((long long)b * a.I + t) * Li, Li), t);
+    if (masked && t < a.C) vv_le_best_take(mk, vv_le_dist(z, msk, a.prior_cat + (long long)t * Lc, Lc), t);
+    const int i0 = vv_le_block_argmin(cat, red), i1 = vv_le_block_argmin(inst, red);
     int i2 = i0, i3 = i0;
     if (masked) {                                       // uniform over the workgroup
-        i2 = mm_block_argmin(mk, red);
+        i2 = vv_le_block_argmin(mk, red);
         if (t < L) {
             const float v = t < Lc ? vv_mm_correct(msk[t], a.prior_cat[(long long)i2 * Lc + t], a.eps2[(long long)b * Lc + t], z[t]) : z[t];
             if (t < Lc) corr[t] = v;
             a.z_corr[(long long)b * L + t] = v;
-            vv_mm_store_act(a.z_corr_act, a.act_dtype, (long long)b * L + t, v);
+            vv_le_store_act(a.z_corr_act, a.act_dtype, (long long)b * L + t, v);
         }
         __syncthreads();
-        if (t < a.C) vv_mm_best_take(cor, vv_mm_dist(corr, nullptr, a.prior_cat + (long long)t * Lc, Lc), t);
-        i3 = mm_block_argmin(cor, red);
+        if (t < a.C) vv_le_best_take(cor, vv_le_dist(corr, nullptr, a.prior_cat + (long long)t * Lc, Lc), t);
+        i3 = vv_le_block_argmin(cor, red);
     }
     if (t == 0) {
         int *ix = a.idx + (long long)b * 4;
@@ -102,17 +86,17 @@ __global__ __launch_bounds__(VV_MM_THREADS) void mm_train_fwd_kernel(const VvMmT
     __shared__ float term[2 * VV_MM_MAX_L], pc[VV_MM_THREADS], pi[VV_MM_THREADS];
     const int t = threadIdx.x, i = blockIdx.x, Lc = a.Lc, L = Lc + a.Li;
     if (t < L) {
-        const VvMmElem v = vv_mm_elem(a, i, t);
-        const float zi = vv_mm_z_in(v);
+        const VvLeElem v = vv_mm_elem(a, i, t);
+        const float zi = vv_le_z_in(v);
         a.z_in[(long long)i * L + t] = zi;
-        vv_mm_store_act(a.z_in_act, a.act_dtype, (long long)i * L + t, zi);
-        term[t] = vv_mm_kl_term(v);
+        vv_le_store_act(a.z_in_act, a.act_dtype, (long long)i * L + t, zi);
+        term[t] = vv_le_kl_term(v);
     }
     const int n = vv_mm_partials(a.B);
     if (t < n) vv_mm_reg_partial(a, i, t, pc[t], pi[t]);
     __syncthreads();
-    if (t == 0) a.kl[i] = vv_mm_sum(term, Lc) + vv_mm_sum(term + Lc, a.Li);
-    if (t == 64) a.reg[i] = vv_mm_sum(pc, n) + vv_mm_sum(pi, n);
+    if (t == 0) a.kl[i] = vv_le_sum(term, Lc) + vv_le_sum(term + Lc, a.Li);
+    if (t == 64) a.reg[i] = vv_le_sum(pc, n) + vv_le_sum(pi, n);
 }
 
 __global__ __launch_bounds__(VV_MM_THREADS) void mm_train_bwd_kernel(const VvMmTrain a) {
@@ -122,7 +106,7 @@ __global__ __launch_bounds__(VV_MM_THREADS) void mm_train_bwd_kernel(const VvMmT
     float am = 0.0f, alv = 0.0f, mi = 0.0f, lvi = 0.0f, ei = 1.0f;
     if (t < L) {
         vv_mm_prior_at(a, i, t, mi, lvi);
-        ei = vv_det_exp(0.5f * lvi);
+        ei = vv_le_scale(lvi);
     }
     for (int j0 = 0; j0 < a.B; j0 += VV_MM_THREADS) {
         const int n = a.B - j0 < VV_MM_THREADS ? a.B - j0 : VV_MM_THREADS;
@@ -135,7 +119,7 @@ __global__ __launch_bounds__(VV_MM_THREADS) void mm_train_bwd_kernel(const VvMmT
             for (int k = 0; k < n; ++k) {
                 float mj, lvj;
                 vv_mm_prior_at(a, j0 + k, t, mj, lvj);
-                vv_mm_pair_accumulate(am, alv, g[2 * grp][k], g[2 * grp + 1][k], mi, mj, ei, lvj);
+                vv_le_pair_accumulate(am, alv, g[2 * grp][k], g[2 * grp + 1][k], mi, mj, ei, vv_le_scale(lvj));
             }
         }
         __syncthreads();
@@ -143,8 +127,7 @@ __global__ __launch_bounds__(VV_MM_THREADS) void mm_train_bwd_kernel(const VvMmT
     if (t < L) vv_mm_bwd_store(a, i, t, am, alv);
 }
 
-inline bool mm_misaligned(const void *p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-inline bool mm_dims_ok(int B, int Lc, int Li) { return B >= 1 && Lc >= 1 && Lc <= VV_MM_MAX_L && Li >= 1 && Li <= VV_MM_MAX_L; }
+inline bool mm_dims_ok(int B, int Lc, int Li) { return vv_le_dims_ok(B, Lc, VV_MM_MAX_L) && vv_le_dims_ok(B, Li, VV_MM_MAX_L); }
 inline bool mm_count_ok(int n) { return n >= 1 && n <= VV_MM_MAX_C; }
 
 int mm_eval_check(const VvMmEval &a) {
@@ -157,9 +140,9 @@ int mm_eval_check(const VvMmEval &a) {
     if ((a.z_act || a.z_corr_act) && !vv_dtype_in<float, __bf16>(a.act_dtype)) return VV_ERR_DTYPE;
     const void *f32s[] = {a.enc_out, a.eps, a.mask, a.eps2, a.prior_cat, a.prior_inst, a.cat_onehot, a.inst_onehot, a.z, a.z_corr, a.idx, a.acc};
     for (const void *p : f32s)
-        if (mm_misaligned(p, 3u)) return VV_ERR_ALIGN;
+        if (vv_le_misaligned(p, 3u)) return VV_ERR_ALIGN;
     const unsigned am = a.act_dtype == VV_BF16 ? 1u : 3u;
-    if (mm_misaligned(a.z_act, am) || mm_misaligned(a.z_corr_act, am)) return VV_ERR_ALIGN;
+    if (vv_le_misaligned(a.z_act, am) || vv_le_misaligned(a.z_corr_act, am)) return VV_ERR_ALIGN;
     return VV_OK;
 }
 
@@ -173,20 +156,32 @@ int mm_train_check(const VvMmTrain &a, bool bwd) {
     const void *f32s[] = {a.enc_out, a.eps, a.mean_cp, a.lv_cp, a.mean_ip, a.lv_ip, a.eps_p, a.noise, a.cat_onehot, a.dz_in, a.z_in, a.kl, a.reg,
                           a.d_enc_out, a.d_mean_cp, a.d_lv_cp, a.d_mean_ip, a.d_lv_ip};
     for (const void *p : f32s)
-        if (mm_misaligned(p, 3u)) return VV_ERR_ALIGN;
-    if (mm_misaligned(a.z_in_act, a.act_dtype == VV_BF16 ? 1u : 3u)) return VV_ERR_ALIGN;
+        if (vv_le_misaligned(p, 3u)) return VV_ERR_ALIGN;
+    if (vv_le_misaligned(a.z_in_act, a.act_dtype == VV_BF16 ? 1u : 3u)) return VV_ERR_ALIGN;
     return VV_OK;
 }
 
-VvMmEval mm_eval_args(const float *enc_out, const float *eps, const float *mask, const float *eps2, const float *prior_cat,
-                      const float *prior_inst, const float *cat_onehot, const float *inst_onehot, float *z, float *z_corr, void *z_act,
-                      void *z_corr_act, int act_dtype, int *idx, float *acc, int batch, int lc, int li, int classes, int insts) {
+// One body per entry pair: the arguments, the check, and then the launch (host == false) or the host's whole-batch loop.
+int mm_eval(const float *enc_out, const float *eps, const float *mask, const float *eps2, const float *prior_cat, const float *prior_inst,
+            const float *cat_onehot, const float *inst_onehot, float *z, float *z_corr, void *z_act, void *z_corr_act, int act_dtype, int *idx,
+            float *acc, int batch, int lc, int li, int classes, int insts, bool host, void *hip_stream) {
     VvMmEval a;
     a.enc_out = enc_out, a.eps = eps, a.mask = mask, a.eps2 = eps2, a.prior_cat = prior_cat, a.prior_inst = prior_inst;
     a.cat_onehot = cat_onehot, a.inst_onehot = inst_onehot, a.z = z, a.z_corr = z_corr, a.z_act = z_act;
     a.z_corr_act = mask ? z_corr_act : nullptr, a.act_dtype = act_dtype, a.idx = idx, a.acc = acc;
     a.B = batch, a.Lc = lc, a.Li = li, a.C = classes, a.I = insts;
-    return a;
+    const int rc = mm_eval_check(a);
+    if (rc != VV_OK) return rc;
+    if (host) {
+        vv_mm_eval_all(a);
+        return VV_OK;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    VV_LAUNCH(mm_eval_kernel, dim3((unsigned)batch), dim3(VV_MM_THREADS), 0, st, a);
+    const int rl = vv_launch_status();
+    if (rl != VV_OK) return rl;
+    VV_LAUNCH(mm_accuracy_kernel, dim3(1), dim3(VV_MM_THREADS), 0, st, a);
+    return vv_launch_status();
 }
 
 VvMmTrain mm_train_args(const float *enc_out, const float *eps, const float *mean_cp, const float *lv_cp, const float *mean_ip,
@@ -198,82 +193,84 @@ VvMmTrain mm_train_args(const float *enc_out, const float *eps, const float *mea
     return a;
 }
 
+// checks a, then runs the forward (bwd == false) or the backward as one launch or as the host's loop over the samples
+int mm_train(const VvMmTrain &a, bool bwd, bool host, void *hip_stream) {
+    const int rc = mm_train_check(a, bwd);
+    if (rc != VV_OK) return rc;
+    if (host) {
+        for (int i = 0; i < a.B; ++i) bwd ? vv_mm_train_bwd_sample(a, i) : vv_mm_train_fwd_sample(a, i);
+        return VV_OK;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    if (bwd) VV_LAUNCH(mm_train_bwd_kernel, dim3((unsigned)a.B), dim3(VV_MM_THREADS), 0, st, a);
+    else VV_LAUNCH(mm_train_fwd_kernel, dim3((unsigned)a.B), dim3(VV_MM_THREADS), 0, st, a);
+    return vv_launch_status();
+}
+
+int mm_train_fwd(const float *enc_out, const float *eps, const float *mean_cp, const float *lv_cp, const float *mean_ip, const float *lv_ip,
+                 const float *eps_p, const float *noise, const float *cat_onehot, float *z_in, void *z_in_act, int act_dtype, float *kl,
+                 float *reg, int batch, int lc, int li, int classes, bool host, void *hip_stream) {
+    VvMmTrain a = mm_train_args(enc_out, eps, mean_cp, lv_cp, mean_ip, lv_ip, eps_p, noise, cat_onehot, batch, lc, li, classes);
+    a.z_in = z_in, a.z_in_act = z_in_act, a.act_dtype = act_dtype, a.kl = kl, a.reg = reg;
+    return mm_train(a, false, host, hip_stream);
+}
+
+int mm_train_bwd(const float *enc_out, const float *eps, const float *mean_cp, const float *lv_cp, const float *mean_ip, const float *lv_ip,
+                 const float *eps_p, const float *noise, const float *cat_onehot, const float *dz_in, float inv_batch, float *d_enc_out,
+                 float *d_mean_cp, float *d_lv_cp, float *d_mean_ip, float *d_lv_ip, int batch, int lc, int li, int classes, bool host,
+                 void *hip_stream) {
+    VvMmTrain a = mm_train_args(enc_out, eps, mean_cp, lv_cp, mean_ip, lv_ip, eps_p, noise, cat_onehot, batch, lc, li, classes);
+    a.dz_in = dz_in, a.inv_batch = inv_batch, a.d_enc_out = d_enc_out, a.d_mean_cp = d_mean_cp, a.d_lv_cp = d_lv_cp;
+    a.d_mean_ip = d_mean_ip, a.d_lv_ip = d_lv_ip;
+    return mm_train(a, true, host, hip_stream);
+}
+
 }  // namespace
 
 VV_EXPORT int vv_mm_latent_eval(const float *enc_out, const float *eps, const float *mask, const float *eps2, const float *prior_cat,
                                 const float *prior_inst, const float *cat_onehot, const float *inst_onehot, float *z, float *z_corr,
                                 void *z_act, void *z_corr_act, int act_dtype, int *idx, float *acc, int batch, int lc, int li, int classes,
                                 int insts, void *hip_stream) {
-    const VvMmEval a = mm_eval_args(enc_out, eps, mask, eps2, prior_cat, prior_inst, cat_onehot, inst_onehot, z, z_corr, z_act, z_corr_act,
-                                    act_dtype, idx, acc, batch, lc, li, classes, insts);
-    const int rc = mm_eval_check(a);
-    if (rc != VV_OK) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    VV_LAUNCH(mm_eval_kernel, dim3((unsigned)batch), dim3(VV_MM_THREADS), 0, st, a);
-    const int rl = vv_launch_status();
-    if (rl != VV_OK) return rl;
-    VV_LAUNCH(mm_accuracy_kernel, dim3(1), dim3(VV_MM_THREADS), 0, st, a);
-    return vv_launch_status();
+    return mm_eval(enc_out, eps, mask, eps2, prior_cat, prior_inst, cat_onehot, inst_onehot, z, z_corr, z_act, z_corr_act, act_dtype, idx, acc,
+                   batch, lc, li, classes, insts, false, hip_stream);
 }
 
 VV_EXPORT int vv_mm_latent_eval_host(const float *enc_out, const float *eps, const float *mask, const float *eps2, const float *prior_cat,
                                      const float *prior_inst, const float *cat_onehot, const float *inst_onehot, float *z, float *z_corr,
                                      void *z_act, void *z_corr_act, int act_dtype, int *idx, float *acc, int batch, int lc, int li,
                                      int classes, int insts) {
-    const VvMmEval a = mm_eval_args(enc_out, eps, mask, eps2, prior_cat, prior_inst, cat_onehot, inst_onehot, z, z_corr, z_act, z_corr_act,
-                                    act_dtype, idx, acc, batch, lc, li, classes, insts);
-    const int rc = mm_eval_check(a);
-    if (rc != VV_OK) return rc;
-    vv_mm_eval_all(a);
-    return VV_OK;
+    return mm_eval(enc_out, eps, mask, eps2, prior_cat, prior_inst, cat_onehot, inst_onehot, z, z_corr, z_act, z_corr_act, act_dtype, idx, acc,
+                   batch, lc, li, classes, insts, true, nullptr);
 }
 
 VV_EXPORT int vv_mm_latent_train_fwd(const float *enc_out, const float *eps, const float *mean_cp, const float *lv_cp, const float *mean_ip,
                                      const float *lv_ip, const float *eps_p, const float *noise, const float *cat_onehot, float *z_in,
                                      void *z_in_act, int act_dtype, float *kl, float *reg, int batch, int lc, int li, int classes,
                                      void *hip_stream) {
-    VvMmTrain a = mm_train_args(enc_out, eps, mean_cp, lv_cp, mean_ip, lv_ip, eps_p, noise, cat_onehot, batch, lc, li, classes);
-    a.z_in = z_in, a.z_in_act = z_in_act, a.act_dtype = act_dtype, a.kl = kl, a.reg = reg;
-    const int rc = mm_train_check(a, false);
-    if (rc != VV_OK) return rc;
-    VV_LAUNCH(mm_train_fwd_kernel, dim3((unsigned)batch), dim3(VV_MM_THREADS), 0, reinterpret_cast<hipStream_t>(hip_stream), a);
-    return vv_launch_status();
+    return mm_train_fwd(enc_out, eps, mean_cp, lv_cp, mean_ip, lv_ip, eps_p, noise, cat_onehot, z_in, z_in_act, act_dtype, kl, reg, batch, lc, li,
+                        classes, false, hip_stream);
 }
 
 VV_EXPORT int vv_mm_latent_train_fwd_host(const float *enc_out, const float *eps, const float *mean_cp, const float *lv_cp,
                                           const float *mean_ip, const float *lv_ip, const float *eps_p, const float *noise,
                                           const float *cat_onehot, float *z_in, void *z_in_act, int act_dtype, float *kl, float *reg,
                                           int batch, int lc, int li, int classes) {
-    VvMmTrain a = mm_train_args(enc_out, eps, mean_cp, lv_cp, mean_ip, lv_ip, eps_p, noise, cat_onehot, batch, lc, li, classes);
-    a.z_in = z_in, a.z_in_act = z_in_act, a.act_dtype = act_dtype, a.kl = kl, a.reg = reg;
-    const int rc = mm_train_check(a, false);
-    if (rc != VV_OK) return rc;
-    for (int i = 0; i < batch; ++i) vv_mm_train_fwd_sample(a, i);
-    return VV_OK;
+    return mm_train_fwd(enc_out, eps, mean_cp, lv_cp, mean_ip, lv_ip, eps_p, noise, cat_onehot, z_in, z_in_act, act_dtype, kl, reg, batch, lc, li,
+                        classes, true, nullptr);
 }
 
 VV_EXPORT int vv_mm_latent_train_bwd(const float *enc_out, const float *eps, const float *mean_cp, const float *lv_cp, const float *mean_ip,
                                      const float *lv_ip, const float *eps_p, const float *noise, const float *cat_onehot,
                                      const float *dz_in, float inv_batch, float *d_enc_out, float *d_mean_cp, float *d_lv_cp,
                                      float *d_mean_ip, float *d_lv_ip, int batch, int lc, int li, int classes, void *hip_stream) {
-    VvMmTrain a = mm_train_args(enc_out, eps, mean_cp, lv_cp, mean_ip, lv_ip, eps_p, noise, cat_onehot, batch, lc, li, classes);
-    a.dz_in = dz_in, a.inv_batch = inv_batch, a.d_enc_out = d_enc_out, a.d_mean_cp = d_mean_cp, a.d_lv_cp = d_lv_cp;
-    a.d_mean_ip = d_mean_ip, a.d_lv_ip = d_lv_ip;
-    const int rc = mm_train_check(a, true);
-    if (rc != VV_OK) return rc;
-    VV_LAUNCH(mm_train_bwd_kernel, dim3((unsigned)batch), dim3(VV_MM_THREADS), 0, reinterpret_cast<hipStream_t>(hip_stream), a);
-    return vv_launch_status();
+    return mm_train_bwd(enc_out, eps, mean_cp, lv_cp, mean_ip, lv_ip, eps_p, noise, cat_onehot, dz_in, inv_batch, d_enc_out, d_mean_cp, d_lv_cp,
+                        d_mean_ip, d_lv_ip, batch, lc, li, classes, false, hip_stream);
 }
 
 VV_EXPORT int vv_mm_latent_train_bwd_host(const float *enc_out, const float *eps, const float *mean_cp, const float *lv_cp,
                                           const float *mean_ip, const float *lv_ip, const float *eps_p, const float *noise,
                                           const float *cat_onehot, const float *dz_in, float inv_batch, float *d_enc_out, float *d_mean_cp,
                                           float *d_lv_cp, float *d_mean_ip, float *d_lv_ip, int batch, int lc, int li, int classes) {
-    VvMmTrain a = mm_train_args(enc_out, eps, mean_cp, lv_cp, mean_ip, lv_ip, eps_p, noise, cat_onehot, batch, lc, li, classes);
-    a.dz_in = dz_in, a.inv_batch = inv_batch, a.d_enc_out = d_enc_out, a.d_mean_cp = d_mean_cp, a.d_lv_cp = d_lv_cp;
-    a.d_mean_ip = d_mean_ip, a.d_lv_ip = d_lv_ip;
-    const int rc = mm_train_check(a, true);
-    if (rc != VV_OK) return rc;
-    for (int i = 0; i < batch; ++i) vv_mm_train_bwd_sample(a, i);
-    return VV_OK;
+    return mm_train_bwd(enc_out, eps, mean_cp, lv_cp, mean_ip, lv_ip, eps_p, noise, cat_onehot, dz_in, inv_batch, d_enc_out, d_mean_cp, d_lv_cp,
+                        d_mean_ip, d_lv_ip, batch, lc, li, classes, true, nullptr);
 }

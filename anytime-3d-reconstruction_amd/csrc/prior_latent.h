@@ -8,17 +8,18 @@
 //
 // The head output of one sample is [mean (L) | logVar (L)]; every other array is [B, L] (the prior table of the evaluation: [I, L]).
 //
-// Same bits on both sides.  The scalar helpers are mm_latent.h's: float32 +, -, *, the correctly rounded division and square root,
-// comparisons and bit operations, contraction OFF in every function, exp from detect_decode.h.  Every sum runs in ONE ascending order:
+// Same bits on both sides.  The arithmetic of one latent element is latent_elem.h's, shared with mm_latent.h: float32 +, -, *, the
+// correctly rounded division and square root, comparisons and bit operations, contraction OFF in every function, exp from
+// detect_decode.h.  Every sum runs in ONE ascending order:
 // over a latent's elements l = 0 .. L-1, over the prior table's rows, and over the batch j = 0 .. B-1 (the regulariser's pairs, forward
 // and backward) -- the device walks the batch in pieces of VV_PL_PIECE rows staged in LDS and carries the running sum from piece to
 // piece, so the order does not depend on the piece size.
 //
 // No inline assembly, no atomics, no memory besides the arguments.
 #pragma once
-#include "mm_latent.h"
+#include "latent_elem.h"
 
-#define VV_PL_HD VV_MM_HD
+#define VV_PL_HD VV_LE_HD
 
 constexpr int VV_PL_MAX_L = 64;          // width of the latent
 constexpr int VV_PL_MAX_I = 256;         // rows of the evaluation's prior table
@@ -37,63 +38,33 @@ struct VvPlTrain {
     int B, L;
 };
 
-// what element e of sample b reads, in mm_latent.h's terms (its kl term and sampling apply unchanged)
-VV_PL_HD VvMmElem vv_pl_elem(const VvPlTrain &a, int b, int e) {
+// what element e of sample b reads
+VV_PL_HD VvLeElem vv_pl_elem(const VvPlTrain &a, int b, int e) {
     const float *row = a.enc_out + (long long)b * (2 * a.L);
     const long long le = (long long)b * a.L + e;
-    VvMmElem v;
+    VvLeElem v;
     v.mean = row[e], v.raw = row[a.L + e];
-    v.lv = vv_mm_clip(v.raw);
+    v.lv = vv_le_clip(v.raw);
     v.mt = a.mean_p[le], v.lvt = a.lv_p[le];
     v.eps = a.eps[le], v.eps_p = a.eps_p[le];
     v.from_prior = a.keep ? !(a.keep[le] == 1.0f) : false;            // tf.where(keep == 1., z, z_prior) (:1047)
     v.dz = a.dz_in ? a.dz_in[le] : 0.0f;
     return v;
 }
-// the scale of row i's distances: exp(0.5 lv) (function.py:50)
-VV_PL_HD float vv_pl_scale(float lv) {
-#pragma clang fp contract(off)
-    return vv_det_exp(0.5f * lv);
-}
 // sum_l |m_i - m_j|_l / scale_l in index order (function.py:49-50): the scale is row i's
 VV_PL_HD float vv_pl_pair_dist(const float *mi, const float *mj, const float *scale, int L) {
 #pragma clang fp contract(off)
     float d = 0.0f;
-    for (int l = 0; l < L; ++l) d = d + vv_mm_abs(mi[l] - mj[l]) / scale[l];
+    for (int l = 0; l < L; ++l) d = d + vv_le_abs(mi[l] - mj[l]) / scale[l];
     return d;
-}
-// pair (i, j)'s share of d reg / d mean_i[l] and d reg / d lv_i[l], given both scales; the derivative of |x| at 0 is 0
-VV_PL_HD void vv_pl_pair_accumulate(float &am, float &alv, float gij, float gji, float mi, float mj, float ei, float ej) {
-#pragma clang fp contract(off)
-    const float diff = mi - mj;
-    if (diff == 0.0f) return;
-    const float sgn = diff > 0.0f ? 1.0f : (diff < 0.0f ? -1.0f : diff);      // a NaN stays
-    am = am + (gij * sgn) / ei;
-    am = am + (gji * sgn) / ej;
-    alv = alv + (gij * -0.5f) * (vv_mm_abs(diff) / ei);
 }
 // element e of sample i, given the accumulated regulariser sums: d_enc_out's two entries and the prior's two
 VV_PL_HD void vv_pl_bwd_store(const VvPlTrain &a, int i, int e, float am, float alv) {
-#pragma clang fp contract(off)
-    const VvMmElem v = vv_pl_elem(a, i, e);
-    const float ex = vv_det_exp(v.lv), et = vv_det_exp(v.lvt), d = v.mean - v.mt;
-    const float kl_mean = d / et;                                              // d kl / d mean; the prior mean gets the negative
-    const float kl_lv = ex / (2.0f * et) - 0.5f;
-    const float kl_lvt = 0.5f - (ex + d * d) / (2.0f * et);
-    float g_mean = kl_mean * a.inv_batch, g_lv = kl_lv * a.inv_batch;
-    float g_mt = (a.reg_weight * am - kl_mean) * a.inv_batch, g_lvt = (kl_lvt + a.reg_weight * alv) * a.inv_batch;
-    if (v.from_prior) {
-        g_mt = g_mt + v.dz;
-        g_lvt = g_lvt + v.dz * ((0.5f * vv_mm_std(v.lvt)) * v.eps_p);
-    } else {
-        g_mean = g_mean + v.dz;
-        g_lv = g_lv + v.dz * ((0.5f * vv_mm_std(v.lv)) * v.eps);
-    }
-    if (!vv_mm_clip_passes(v.raw)) g_lv = 0.0f;
+    const VvLeGrads g = vv_le_elem_grads(vv_pl_elem(a, i, e), am, alv, a.reg_weight, a.inv_batch);
     float *row = a.d_enc_out + (long long)i * (2 * a.L);
-    row[e] = g_mean, row[a.L + e] = g_lv;
-    if (a.d_mean_p) a.d_mean_p[(long long)i * a.L + e] = g_mt;
-    if (a.d_lv_p) a.d_lv_p[(long long)i * a.L + e] = g_lvt;
+    row[e] = g.mean, row[a.L + e] = g.lv;
+    if (a.d_mean_p) a.d_mean_p[(long long)i * a.L + e] = g.mt;
+    if (a.d_lv_p) a.d_lv_p[(long long)i * a.L + e] = g.lvt;
 }
 
 // one sample as plain loops
@@ -102,17 +73,17 @@ VV_PL_HD void vv_pl_train_fwd_sample(const VvPlTrain &a, int i) {
     const int L = a.L;
     float term[VV_PL_MAX_L], ei[VV_PL_MAX_L];
     for (int e = 0; e < L; ++e) {
-        const VvMmElem v = vv_pl_elem(a, i, e);
-        const float zi = vv_mm_z_in(v);
+        const VvLeElem v = vv_pl_elem(a, i, e);
+        const float zi = vv_le_z_in(v);
         a.z_in[(long long)i * L + e] = zi;
-        if (a.z_in_bf16) a.z_in_bf16[(long long)i * L + e] = vv_mm_bf16(zi);
-        term[e] = vv_mm_kl_term(v);
-        ei[e] = vv_pl_scale(v.lvt);
+        if (a.z_in_bf16) a.z_in_bf16[(long long)i * L + e] = vv_le_bf16(zi);
+        term[e] = vv_le_kl_term(v);
+        ei[e] = vv_le_scale(v.lvt);
     }
-    a.kl[i] = vv_mm_sum(term, L);
+    a.kl[i] = vv_le_sum(term, L);
     float s = 0.0f;
     for (int j = 0; j < a.B; ++j)
-        s = s + vv_mm_hinge(vv_pl_pair_dist(a.mean_p + (long long)i * L, a.mean_p + (long long)j * L, ei, L) - a.dist);
+        s = s + vv_le_hinge(vv_pl_pair_dist(a.mean_p + (long long)i * L, a.mean_p + (long long)j * L, ei, L) - a.dist);
     a.reg[i] = s;
 }
 VV_PL_HD void vv_pl_train_bwd_sample(const VvPlTrain &a, int i) {
@@ -120,13 +91,13 @@ VV_PL_HD void vv_pl_train_bwd_sample(const VvPlTrain &a, int i) {
     const int L = a.L;
     const float *mi = a.mean_p + (long long)i * L;
     float ei[VV_PL_MAX_L], ej[VV_PL_MAX_L], am[VV_PL_MAX_L], alv[VV_PL_MAX_L];
-    for (int e = 0; e < L; ++e) ei[e] = vv_pl_scale(a.lv_p[(long long)i * L + e]), am[e] = 0.0f, alv[e] = 0.0f;
+    for (int e = 0; e < L; ++e) ei[e] = vv_le_scale(a.lv_p[(long long)i * L + e]), am[e] = 0.0f, alv[e] = 0.0f;
     for (int j = 0; j < a.B; ++j) {
         const float *mj = a.mean_p + (long long)j * L;
-        for (int e = 0; e < L; ++e) ej[e] = vv_pl_scale(a.lv_p[(long long)j * L + e]);
-        const float gij = vv_mm_hinge_grad(vv_pl_pair_dist(mi, mj, ei, L) - a.dist);
-        const float gji = vv_mm_hinge_grad(vv_pl_pair_dist(mj, mi, ej, L) - a.dist);
-        for (int e = 0; e < L; ++e) vv_pl_pair_accumulate(am[e], alv[e], gij, gji, mi[e], mj[e], ei[e], ej[e]);
+        for (int e = 0; e < L; ++e) ej[e] = vv_le_scale(a.lv_p[(long long)j * L + e]);
+        const float gij = vv_le_hinge_grad(vv_pl_pair_dist(mi, mj, ei, L) - a.dist);
+        const float gji = vv_le_hinge_grad(vv_pl_pair_dist(mj, mi, ej, L) - a.dist);
+        for (int e = 0; e < L; ++e) vv_le_pair_accumulate(am[e], alv[e], gij, gji, mi[e], mj[e], ei[e], ej[e]);
     }
     for (int e = 0; e < L; ++e) vv_pl_bwd_store(a, i, e, am[e], alv[e]);
 }
@@ -144,7 +115,7 @@ VV_PL_HD float vv_pl_eval_z(const VvPlEval &a, int b, int e) {
 #pragma clang fp contract(off)
     const float *row = a.enc_out + (long long)b * (2 * a.L);
     const long long le = (long long)b * a.L + e;
-    const float z = vv_mm_sample(row[e], vv_mm_clip(row[a.L + e]), a.eps[le]);
+    const float z = vv_le_sample(row[e], vv_le_clip(row[a.L + e]), a.eps[le]);
     if (!a.mask) return z;
     const float v = z * a.mask[le];
     return v == 0.0f ? a.fill[le] : v;
@@ -153,16 +124,16 @@ VV_PL_HD void vv_pl_eval_store(const VvPlEval &a, int b, int e, float z, int idx
     const long long le = (long long)b * a.L + e;
     const float c = a.prior[(long long)idx * a.L + e];                         // z_corrected = prior[idx], the whole row (:474)
     a.z[le] = z, a.z_corr[le] = c;
-    if (a.z_bf16) a.z_bf16[le] = vv_mm_bf16(z);
-    if (a.z_corr_bf16) a.z_corr_bf16[le] = vv_mm_bf16(c);
+    if (a.z_bf16) a.z_bf16[le] = vv_le_bf16(z);
+    if (a.z_corr_bf16) a.z_corr_bf16[le] = vv_le_bf16(c);
 }
 VV_PL_HD void vv_pl_eval_sample(const VvPlEval &a, int b) {
     float z[VV_PL_MAX_L];
     for (int e = 0; e < a.L; ++e) z[e] = vv_pl_eval_z(a, b, e);
     const float *m = a.mask ? a.mask + (long long)b * a.L : nullptr;
-    VvMmBest best = vv_mm_best_init();
-    for (int c = 0; c < a.I; ++c) vv_mm_best_take(best, vv_mm_dist(z, m, a.prior + (long long)c * a.L, a.L), c);   // :460-462
-    const int ix = vv_mm_best_index(best);
+    VvLeBest best = vv_le_best_init();
+    for (int c = 0; c < a.I; ++c) vv_le_best_take(best, vv_le_dist(z, m, a.prior + (long long)c * a.L, a.L), c);   // :460-462
+    const int ix = vv_le_best_index(best);
     a.idx[b] = ix;
     for (int e = 0; e < a.L; ++e) vv_pl_eval_store(a, b, e, z[e], ix);
 }

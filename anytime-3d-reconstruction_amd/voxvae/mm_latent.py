@@ -10,7 +10,7 @@ import torch
 
 from . import lib as _L
 from . import train as _T
-from .prior_latent import _check
+from .prior_latent import _check, stage_node
 
 
 def _st():
@@ -74,31 +74,12 @@ def eval(enc_out, eps, mask, eps2, prior_cat, prior_inst, cat_onehot, inst_oneho
     return z, zc, z_act, zc_act, idx, acc
 
 
-class _LatentStage(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, enc_out, mean_cp, lv_cp, mean_ip, lv_ip, eps, eps_p, noise, cat_onehot, bf16):
-        e, *pri4 = (t.detach().float().contiguous() for t in (enc_out, mean_cp, lv_cp, mean_ip, lv_ip))
-        z_in, twin, kl, reg = train_fwd(e, eps, pri4, eps_p, noise, cat_onehot, bf16)
-        ctx.saved = (e, eps, pri4, eps_p, noise, cat_onehot)
-        extra = kl.mean() + reg.mean()
-        if twin is None:
-            twin = z_in.new_empty(0)
-        ctx.mark_non_differentiable(kl, reg, twin)            # one call: a second one would replace the first one's set
-        return z_in, extra, kl, reg, twin
-
-    @staticmethod
-    def backward(ctx, dz, _d_extra, _d_kl, _d_reg, _d_twin):
-        e, eps = ctx.saved[:2]
-        dz = torch.zeros_like(eps) if dz is None else dz.contiguous()
-        d = train_bwd(*ctx.saved, dz, 1.0 / e.shape[0], want=ctx.needs_input_grad[1:5])
-        return ((d[0] if ctx.needs_input_grad[0] else None),) + d[1:] + (None,) * 5
-
-
 def latent_stage(enc_out, mean_cp, lv_cp, mean_ip, lv_ip, eps, eps_p, noise, cat_onehot, bf16=False):
     """The training stage as one autograd node -> (z_in [B, Lc+Li], extra, kl [B], reg [B], bfloat16 twin of z_in or None), with
     extra = mean_b kl + mean_b reg.  Forward is ONE vv_mm_latent_train_fwd; backward is ONE vv_mm_latent_train_bwd that takes the
     gradient arriving at z_in as d shape / d z_in and gives the gradients of enc_out and the four prior tensors (one that does not
     require a gradient -- a constant log-variance -- gets a NULL output).  The gradient arriving at `extra` is taken to be 1, as in
     voxvae.prior_latent.latent_stage; kl, reg and the twin carry none."""
-    z_in, extra, kl, reg, twin = _LatentStage.apply(enc_out, mean_cp, lv_cp, mean_ip, lv_ip, eps, eps_p, noise, cat_onehot, bool(bf16))
-    return z_in, extra, kl, reg, (twin if bf16 else None)
+    fwd = lambda e, *pri4: train_fwd(e, eps, pri4, eps_p, noise, cat_onehot, bf16)
+    bwd = lambda e, mc, lc, mi, li, dz, want: train_bwd(e, eps, (mc, lc, mi, li), eps_p, noise, cat_onehot, dz, 1.0 / e.shape[0], want=want)
+    return stage_node(fwd, bwd, None, bf16, enc_out, mean_cp, lv_cp, mean_ip, lv_ip)

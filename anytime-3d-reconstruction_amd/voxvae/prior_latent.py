@@ -76,13 +76,15 @@ def inst_eval(enc_out, eps, mask, fill, prior, bf16=False):
 
 
 class _LatentStage(torch.autograd.Function):
+    """The node of both learned-prior stages (voxvae.mm_latent.latent_stage is the other caller).  leaves: enc_out, then the prior
+    tensors.  fwd(*leaves) -> (z_in, twin or None, kl, reg) and bwd(*leaves, dz, want) -> (d_enc_out, the prior gradients or None) are a
+    stage's train_fwd / train_bwd with everything else bound; want[k]: prior tensor k needs its gradient.  reg_weight None: 1."""
     @staticmethod
-    def forward(ctx, enc_out, mean_p, lv_p, eps, eps_p, keep, dist, reg_weight, bf16):
-        e, m, lv = (t.detach().float().contiguous() for t in (enc_out, mean_p, lv_p))
-        z_in, twin, kl, reg = train_fwd(e, eps, m, lv, eps_p, keep, dist, bf16)
-        ctx.saved = (e, m, lv, eps, eps_p, keep)
-        ctx.consts = (float(dist), float(reg_weight))
-        extra = kl.mean() + float(reg_weight) * reg.mean()
+    def forward(ctx, fwd, bwd, reg_weight, *leaves):
+        ctx.bwd, ctx.leaves = bwd, [t.detach().float().contiguous() for t in leaves]
+        z_in, twin, kl, reg = fwd(*ctx.leaves)
+        ctx.z_shape = z_in.shape
+        extra = kl.mean() + (reg.mean() if reg_weight is None else float(reg_weight) * reg.mean())
         if twin is None:
             twin = z_in.new_empty(0)
         ctx.mark_non_differentiable(kl, reg, twin)            # one call: a second one would replace the first one's set
@@ -90,12 +92,16 @@ class _LatentStage(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz, _d_extra, _d_kl, _d_reg, _d_twin):
-        e, m, lv, eps, eps_p, keep = ctx.saved
-        dist, reg_weight = ctx.consts
-        dz = torch.zeros_like(eps) if dz is None else dz.contiguous()
-        d_e, d_m, d_lv = train_bwd(e, eps, m, lv, eps_p, keep, dist, dz, 1.0 / e.shape[0], reg_weight, want_mean=ctx.needs_input_grad[1],
-                                   want_lv=ctx.needs_input_grad[2])
-        return (d_e if ctx.needs_input_grad[0] else None), d_m, d_lv, None, None, None, None, None, None
+        need = ctx.needs_input_grad[3:]
+        dz = ctx.leaves[0].new_zeros(ctx.z_shape) if dz is None else dz.contiguous()
+        d = ctx.bwd(*ctx.leaves, dz, need[1:])
+        return (None, None, None, (d[0] if need[0] else None)) + tuple(d[1:])
+
+
+def stage_node(fwd, bwd, reg_weight, bf16, *leaves):
+    """_LatentStage over `leaves` -> (z_in, extra, kl, reg, bfloat16 twin of z_in or None)."""
+    z_in, extra, kl, reg, twin = _LatentStage.apply(fwd, bwd, reg_weight, *leaves)
+    return z_in, extra, kl, reg, (twin if bf16 else None)
 
 
 def latent_stage(enc_out, mean_p, lv_p, eps, eps_p, keep, dist, reg_weight, bf16=False):
@@ -104,8 +110,10 @@ def latent_stage(enc_out, mean_p, lv_p, eps, eps_p, keep, dist, reg_weight, bf16
     takes the gradient arriving at z_in as d shape / d z_in and gives the gradients of enc_out, mean_p and lv_p (an input that does not
     require a gradient gets a NULL output).  The gradient arriving at `extra` is taken to be 1 -- what Trainer.step_custom_latent and the
     image models pass; kl, reg and the twin carry none."""
-    z_in, extra, kl, reg, twin = _LatentStage.apply(enc_out, mean_p, lv_p, eps, eps_p, keep, dist, reg_weight, bool(bf16))
-    return z_in, extra, kl, reg, (twin if bf16 else None)
+    dist, reg_weight = float(dist), float(reg_weight)
+    fwd = lambda e, m, lv: train_fwd(e, eps, m, lv, eps_p, keep, dist, bf16)
+    bwd = lambda e, m, lv, dz, want: train_bwd(e, eps, m, lv, eps_p, keep, dist, dz, 1.0 / e.shape[0], reg_weight, *want)
+    return stage_node(fwd, bwd, reg_weight, bf16, enc_out, mean_p, lv_p)
 
 
 class _MaskScale(torch.autograd.Function):

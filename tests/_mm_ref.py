@@ -1,10 +1,10 @@
 """The latent stage of nolboSingleObject (reference nolbo.py:93-147, :183-252; function.py:35-98) restated in numpy float32, with every sum in
 index order (the order csrc/mm_latent.h uses), and the callers of the vv_mm_latent_* entries the tests share.  Held to the fixture
 tests/golden/mm_latent.npz by tests/test_mm_latent_host.py, like the host entries."""
-import ctypes
-
 import numpy as np
 import torch
+
+from _common import _np, _p, _stream, _t, first_argmin as _first_argmin
 
 F = np.float32
 
@@ -15,12 +15,6 @@ def _seq_sum(x):
     for j in range(x.shape[-1]):
         s = (s + x[..., j]).astype(F)
     return s
-
-
-def _first_argmin(d):
-    """First argmin among the distances below +inf; a row without one gets 0."""
-    ok = d < np.inf
-    return np.where(ok.any(axis=-1), np.argmin(np.where(ok, d, np.inf), axis=-1), 0).astype(np.int32)
 
 
 def split(enc, Lc, Li):
@@ -111,22 +105,6 @@ def total_torch(enc, eps, mean_cp, lv_cp, mean_ip, lv_ip, eps_p, noise, cat_oh, 
 
 
 # ---------------------------------------------------------------------------------------------------- callers of the entries
-def _t(x, device):
-    return None if x is None else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(device)
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _np(t):
-    return t.float().cpu().numpy() if t.dtype == torch.bfloat16 else t.cpu().numpy()
-
-
-def _stream(device):
-    return [] if device == 'cpu' else [ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)]
-
-
 def call_eval(L, device, enc, eps, mask, eps2, prior_cat, prior_inst, cat_oh, inst_oh, act=None, lib_call=None):
     """vv_mm_latent_eval (device 'cuda') or vv_mm_latent_eval_host ('cpu') -> dict of numpy outputs; untouched outputs stay NaN / -1."""
     B, (C, Lc), (I, Li) = enc.shape[0], prior_cat.shape, prior_inst.shape[1:]

@@ -2,10 +2,10 @@
 the formulas of the header -- once in float64 (the definition the fixture tests/golden/prior_latent.npz records and the tests hold the
 host entries to) and once in plain float32 numpy (whose distance from the float64 statement sets the tests' gates) -- the same total as
 a torch closure for autograd, and the callers of the entries that the CPU and the GPU tests share."""
-import ctypes
-
 import numpy as np
 import torch
+
+from _common import _np, _p, _stream, _t, first_argmin  # noqa: F401  (first_argmin: also for the tests that import this module)
 
 F = np.float32
 
@@ -29,12 +29,6 @@ def train_fwd(enc, eps, mean_p, lv_p, eps_p, keep, dist, dtype=np.float64):
         d = (np.abs(mean_p[:, None, :] - mean_p[None, :, :]) / np.exp(dtype(0.5) * lv_p)[:, None, :]).sum(-1) - dtype(dist)
         reg = np.where(d > 0, dtype(0), d * d).sum(-1)                # d <= 0 keeps d^2
     return dict(z_in=z_in.astype(dtype), kl=kl.astype(dtype), reg=reg.astype(dtype))
-
-
-def first_argmin(d):
-    """First argmin among the distances below +inf; a row without one gets 0."""
-    ok = d < np.inf
-    return np.where(ok.any(axis=-1), np.argmin(np.where(ok, d, np.inf), axis=-1), 0).astype(np.int32)
 
 
 def inst_eval(enc, eps, mask, fill, prior, dtype=np.float64):
@@ -110,24 +104,8 @@ def eval_args(c):
 
 
 # ---------------------------------------------------------------------------------------------------- callers of the entries
-def _t(x, device):
-    return None if x is None else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(device)
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _np(t):
-    return t.view(torch.int16).cpu().numpy().view(np.uint16) if t.dtype == torch.bfloat16 else t.cpu().numpy()
-
-
 def bf16_to_f32(u16):
     return (u16.astype(np.uint32) << 16).view(np.float32)
-
-
-def _stream(device):
-    return [] if device == 'cpu' else [ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)]
 
 
 def call_train(L, device, c, bf16=False, null_mean=False, null_lv=False):
@@ -146,7 +124,7 @@ def call_train(L, device, c, bf16=False, null_mean=False, null_lv=False):
         torch.cuda.synchronize()
     out = dict(z_in=_np(z_in), kl=_np(kl), reg=_np(reg), d_enc_out=_np(de), d_mean_p=_np(dm), d_lv_p=_np(dlv))
     if bf16:
-        out['z_in_bf16'] = _np(zb)
+        out['z_in_bf16'] = _np(zb, bf16_bits=True)
     return out
 
 
@@ -164,5 +142,5 @@ def call_eval(L, device, c, bf16=False):
         torch.cuda.synchronize()
     out = dict(z=_np(z), z_corr=_np(zc), idx=_np(idx))
     if bf16:
-        out.update(z_bf16=_np(zb), z_corr_bf16=_np(zcb))
+        out.update(z_bf16=_np(zb, bf16_bits=True), z_corr_bf16=_np(zcb, bf16_bits=True))
     return out

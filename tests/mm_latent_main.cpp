@@ -25,7 +25,7 @@ static int run(int B, int Lc, int Li, int C, int I, bool masked, bool hostile, i
     for (float &m : mask) m = draw() > 0.0f ? 1.0f : 0.0f;
     for (int b = 0; b < B; ++b) co[(size_t)b * C + b % C] = 1.0f, io[(size_t)b * I + (b * 7) % I] = 1.0f;
     if (hostile) {
-        enc[0] = vv_det_float(0x7FC00000u), enc[1] = vv_mm_inf(), enc[(size_t)Lc] = 1e30f, enc[(size_t)Lc + 1] = -1e30f;
+        enc[0] = vv_det_float(0x7FC00000u), enc[1] = vv_le_inf(), enc[(size_t)Lc] = 1e30f, enc[(size_t)Lc + 1] = -1e30f;
         pc[0] = vv_det_float(0x7FC00000u);
     }
     std::vector<float> z(B * L), zc(B * L), acc(3);
@@ -64,12 +64,12 @@ static int run(int B, int Lc, int Li, int C, int I, bool masked, bool hostile, i
 
 int main() {
     int rc = 0;
-    rc |= run(1, 1, 1, 1, 1, true, false, VV_MM_F32);
-    rc |= run(1, 7, 12, 12, 10, false, false, VV_MM_BF16);
-    rc |= run(5, 3, 9, 12, 1, true, true, VV_MM_BF16);
-    rc |= run(72, 8, 8, 12, 10, true, false, VV_MM_F32);
-    rc |= run(257, 64, 64, 256, 256, true, false, VV_MM_BF16);
-    rc |= run(300, 5, 64, 3, 256, false, true, VV_MM_F32);
+    rc |= run(1, 1, 1, 1, 1, true, false, VV_LE_F32);
+    rc |= run(1, 7, 12, 12, 10, false, false, VV_LE_BF16);
+    rc |= run(5, 3, 9, 12, 1, true, true, VV_LE_BF16);
+    rc |= run(72, 8, 8, 12, 10, true, false, VV_LE_F32);
+    rc |= run(257, 64, 64, 256, 256, true, false, VV_LE_BF16);
+    rc |= run(300, 5, 64, 3, 256, false, true, VV_LE_F32);
     if (rc) {
         std::printf("FAILED %d\n", rc);
         return 1;

@@ -27,7 +27,7 @@ static int run(int B, int L, int I, bool masked, bool hostile, bool twins) {
         for (int l = 0; l < L; ++l) mp[(size_t)L + l] = mp[l];                 // two samples with identical prior means
     if (hostile) {
         enc[0] = vv_det_float(0x7FC00000u), enc[(size_t)L] = 1e30f;
-        if (n > 1) enc[1] = vv_mm_inf();
+        if (n > 1) enc[1] = vv_le_inf();
         lp[0] = -1e30f;
     }
     std::vector<float> zin(n), kl(B), reg(B), de(2 * n), dm(n), dlv(n);

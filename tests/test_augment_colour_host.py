@@ -3,19 +3,17 @@ vv_augment_draw_ex_host): the blur against scipy, hue/saturation against the num
 order of the four stages, the draws, refusals, datasetUtils.imgAug, and the new host loops as a stand-alone sanitizer program."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 from scipy import ndimage
 
+from _common import build_and_run_sanitized
 import _augment_colour_ref as C
 import _augment_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'anytime-3d-reconstruction_amd')
 
 from voxvae import augment as A          # noqa: E402
 from voxvae import lib as L              # noqa: E402
@@ -324,21 +322,5 @@ def test_image_random_augmentation_routes_through_imgAug_when_asked():
 # ---------------------------------------------------------------------------------------------------------------------- 8. sanitizers
 @pytest.mark.skipif(torch.cuda.is_available(), reason='sanitizer programs run on CPU-only machines')
 def test_standalone_sanitizer_build_of_the_colour_loops(tmp_path):
-    """csrc/augment.h and tests/augment_colour_main.cpp as ONE program of its own with -fsanitize=address,undefined, run on the CPU."""
-    from voxvae import build as vb
-    rocm_clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(vb.HIPCC))), 'llvm', 'bin', 'clang++')
-    compilers = [c for c in (rocm_clang, shutil.which('clang++'), shutil.which('g++')) if c and os.path.exists(c)]
-    assert compilers, 'no C++ compiler found'
-    exe, log = str(tmp_path / 'augment_colour_asan'), ''
-    for cxx in compilers:
-        r = subprocess.run([cxx, '-x', 'c++', '-std=c++17', '-O1', '-g', '-fno-omit-frame-pointer', '-fsanitize=address,undefined',
-                            '-fno-sanitize-recover=all', '-I', os.path.join(PKG, 'csrc'), os.path.join(ROOT, 'tests', 'augment_colour_main.cpp'),
-                            '-o', exe, '-lm'], capture_output=True, text=True)
-        log += '%s: %s\n' % (cxx, r.stderr[-2000:])
-        if r.returncode == 0:
-            break
-    else:
-        pytest.fail('no compiler built the sanitizer program:\n' + log)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith('OK'), r.stdout[-2000:] + r.stderr[-4000:]
-    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr
+    """csrc/augment.h and tests/augment_colour_main.cpp as ONE program of its own under the address and undefined-behaviour sanitizers, run on the CPU."""
+    build_and_run_sanitized('augment_colour_main.cpp', tmp_path, 'augment_colour_asan')

@@ -2,17 +2,16 @@
 arithmetic, validation precedes any launch, the Python engine's plan / permutation / staleness key, and the MAC accounting."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+from _common import build_and_run_sanitized
 import _conv2d_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'anytime-3d-reconstruction_amd')
 F32, BF16 = 0, 1
 NULL, SHAPE, DTYPE = -1, -2, -3
 DARKNET = [(3, 32, 3), (32, 64, 3), (64, 128, 3), (128, 64, 1), (64, 128, 3), (128, 256, 3), (256, 128, 1), (128, 256, 3), (256, 512, 3),
@@ -225,22 +224,5 @@ def test_image_encoder_mac_accounting():
 @pytest.mark.skipif(torch.cuda.is_available(), reason='sanitizer programs run on CPU-only machines')
 def test_plan_header_under_the_host_sanitizers(tmp_path):
     """csrc/conv2d_plan.h compiles for the host: the row split, tap validity, the tap offset and the split-K schedule run in a stand-alone
-    program under -fsanitize=address,undefined (nothing loaded into Python is run under a sanitizer)."""
-    import shutil
-    from voxvae import build as vb
-    rocm_clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(vb.HIPCC))), 'llvm', 'bin', 'clang++')
-    compilers = [c for c in (rocm_clang, shutil.which('clang++'), shutil.which('g++')) if c and os.path.exists(c)]
-    assert compilers, 'no C++ compiler found'
-    exe, log = str(tmp_path / 'conv2d_plan_main'), ''
-    for cxx in compilers:
-        r = subprocess.run([cxx, '-x', 'c++', '-std=c++17', '-O1', '-g', '-fno-omit-frame-pointer', '-fsanitize=address,undefined',
-                            '-fno-sanitize-recover=all', '-I', os.path.join(PKG, 'csrc'), os.path.join(ROOT, 'tests', 'conv2d_plan_main.cpp'),
-                            '-o', exe], capture_output=True, text=True)
-        log += '%s: %s\n' % (cxx, r.stderr[-2000:])
-        if r.returncode == 0:
-            break
-    else:
-        pytest.fail('no compiler built the sanitizer program:\n' + log)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith('OK'), r.stdout[-2000:] + r.stderr[-4000:]
-    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr
+    program under the address and undefined-behaviour sanitizers (nothing loaded into Python is run under a sanitizer)."""
+    build_and_run_sanitized('conv2d_plan_main.cpp', tmp_path, 'conv2d_plan_main')

@@ -3,8 +3,6 @@ the torch modules, the new entries' validation and size queries, the strided ind
 classifier's loss, accuracies and training step."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,11 +10,11 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from _common import build_and_run_sanitized
 import _conv2d_ref as R
 import _darknet53_ref as R53
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'anytime-3d-reconstruction_amd')
 F32, BF16 = 0, 1
 NULL, SHAPE, DTYPE, ALIGN, WORKSPACE = -1, -2, -3, -4, -5
 
@@ -221,23 +219,7 @@ def test_ex_queries(lib):
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason='sanitizer programs run on CPU-only machines')
 def test_strided_plan_under_the_host_sanitizers(tmp_path):
-    from voxvae import build as vb
-    rocm_clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(vb.HIPCC))), 'llvm', 'bin', 'clang++')
-    compilers = [c for c in (rocm_clang, shutil.which('clang++'), shutil.which('g++')) if c and os.path.exists(c)]
-    assert compilers, 'no C++ compiler found'
-    exe, log = str(tmp_path / 'conv2d_s2_plan_main'), ''
-    for cxx in compilers:
-        r = subprocess.run([cxx, '-x', 'c++', '-std=c++17', '-O1', '-g', '-fno-omit-frame-pointer', '-fsanitize=address,undefined',
-                            '-fno-sanitize-recover=all', '-I', os.path.join(PKG, 'csrc'), os.path.join(ROOT, 'tests', 'conv2d_s2_plan_main.cpp'),
-                            '-o', exe], capture_output=True, text=True)
-        log += '%s: %s\n' % (cxx, r.stderr[-2000:])
-        if r.returncode == 0:
-            break
-    else:
-        pytest.fail('no compiler built the sanitizer program:\n' + log)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith('OK'), r.stdout[-2000:] + r.stderr[-4000:]
-    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr
+    build_and_run_sanitized('conv2d_s2_plan_main.cpp', tmp_path, 'conv2d_s2_plan_main')
 
 
 # ------------------------------------------------------------------------------------------------------------ the classifier

@@ -9,17 +9,15 @@ Figures (measured here, recorded in tests/_detect_ref.py and DESIGN 4h):
 """
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from _common import build_and_run_sanitized
 import _detect_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'anytime-3d-reconstruction_amd')
 P, Z, W = 5, 16, 49
 
 
@@ -400,21 +398,5 @@ def test_getpred_tuple_through_the_host_entry(D, P_, Z_):
 # ------------------------------------------------------------------------------------------------------------------ 7. sanitizers
 @pytest.mark.skipif(torch.cuda.is_available(), reason='sanitizer programs run on CPU-only machines')
 def test_standalone_sanitizer_build(tmp_path):
-    """The header and tests/detect_asan_main.cpp as ONE program of its own with -fsanitize=address,undefined, run on the CPU."""
-    from voxvae import build as vb
-    rocm_clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(vb.HIPCC))), 'llvm', 'bin', 'clang++')
-    compilers = [c for c in (rocm_clang, shutil.which('clang++'), shutil.which('g++')) if c and os.path.exists(c)]
-    assert compilers, 'no C++ compiler found'
-    exe, log = str(tmp_path / 'detect_asan'), ''
-    for cxx in compilers:
-        r = subprocess.run([cxx, '-x', 'c++', '-std=c++17', '-O1', '-g', '-fno-omit-frame-pointer', '-fsanitize=address,undefined',
-                            '-fno-sanitize-recover=all', '-I', os.path.join(PKG, 'csrc'), os.path.join(ROOT, 'tests', 'detect_asan_main.cpp'),
-                            '-o', exe, '-lm'], capture_output=True, text=True)
-        log += '%s: %s\n' % (cxx, r.stderr[-2000:])
-        if r.returncode == 0:
-            break
-    else:
-        pytest.fail('no compiler built the sanitizer program:\n' + log)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith('OK'), r.stdout[-2000:] + r.stderr[-4000:]
-    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr
+    """The header and tests/detect_asan_main.cpp as ONE program of its own under the address and undefined-behaviour sanitizers, run on the CPU."""
+    build_and_run_sanitized('detect_asan_main.cpp', tmp_path, 'detect_asan')

@@ -62,7 +62,7 @@ def test_latent_stage_is_train_fwd_and_train_bwd(const_lv, noise, bf16, monkeypa
     for k, got in (('z_in', z_in), ('kl', kl), ('reg', reg), ('d_enc_out', e.grad), ('d_mean_cp', pri[0].grad), ('d_mean_ip', pri[2].grad)) + (
             () if const_lv else (('d_lv_cp', pri[1].grad), ('d_lv_ip', pri[3].grad))):
         _same(got, raw[k], 'raw ' + k)
-    if bf16:                                                            # the twin is vv_mm_bf16 of z_in: round to nearest even on finite values
+    if bf16:                                                            # the twin is vv_le_bf16 of z_in: round to nearest even on finite values
         assert twin.dtype == torch.bfloat16 and bool(torch.isfinite(z_in).all()) and torch.equal(twin, z_in.detach().to(torch.bfloat16))
     else:
         assert twin is None

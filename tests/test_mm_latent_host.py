@@ -7,18 +7,16 @@ Measured on the fixture (largest |host - fixture| over all cases, relative to ma
 reg 4.3e-7; the gates below are 4x these.  Backward: the host entry's error against float64 autograd is at most 2.04x the error float32
 autograd of the same closure makes (gate 4x, computed in the test)."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from _common import build_and_run_sanitized
 import _mm_ref as R
 from voxvae import lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, 'anytime-3d-reconstruction_amd')
 GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'mm_latent.npz')
 Z_GATE, KL_GATE, REG_GATE = 4 * 2.4e-7, 4 * 3.4e-7, 4 * 4.3e-7
 
@@ -242,21 +240,5 @@ def test_null_prior_outputs_and_validation():
 # ------------------------------------------------------------------------------------------------------------------ d. sanitizers
 @pytest.mark.skipif(torch.cuda.is_available(), reason='sanitizer programs run on CPU-only machines')
 def test_standalone_sanitizer_build(tmp_path):
-    """The header and tests/mm_latent_main.cpp as ONE program of its own with -fsanitize=address,undefined, run on the CPU."""
-    from voxvae import build as vb
-    rocm_clang = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(vb.HIPCC))), 'llvm', 'bin', 'clang++')
-    compilers = [c for c in (rocm_clang, shutil.which('clang++'), shutil.which('g++')) if c and os.path.exists(c)]
-    assert compilers, 'no C++ compiler found'
-    exe, log = str(tmp_path / 'mm_latent_asan'), ''
-    for cxx in compilers:
-        r = subprocess.run([cxx, '-x', 'c++', '-std=c++17', '-O1', '-g', '-fno-omit-frame-pointer', '-fsanitize=address,undefined',
-                            '-fno-sanitize-recover=all', '-I', os.path.join(PKG, 'csrc'), os.path.join(ROOT, 'tests', 'mm_latent_main.cpp'),
-                            '-o', exe, '-lm'], capture_output=True, text=True)
-        log += '%s: %s\n' % (cxx, r.stderr[-2000:])
-        if r.returncode == 0:
-            break
-    else:
-        pytest.fail('no compiler built the sanitizer program:\n' + log)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith('OK'), r.stdout[-2000:] + r.stderr[-4000:]
-    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr
+    """The header and tests/mm_latent_main.cpp as ONE program of its own under the address and undefined-behaviour sanitizers, run on the CPU."""
+    build_and_run_sanitized('mm_latent_main.cpp', tmp_path, 'mm_latent_asan')
