@@ -238,12 +238,6 @@ __device__ __forceinline__ void vv_add_shape_metrics(float l, float tp, float fp
 // small.hip (internal): the launch behind vv_shape_metrics, also the last layer's when its partials are reduced separately
 void vv_shape_metrics_launch(const float *stats, float *out4, int batch, hipStream_t st);
 
-// wgrad_phase.hip (internal): phase-form weight gradient of the stride-2 layers; the caller sums *splits slabs.
-bool vv_wgrad_phase_ok(const void *src, const void *g, int batch, int side, int cin, int cout);
-size_t vv_wgrad_phase_ws(long rows, int cin, int cout);
-void vv_wgrad_phase_launch(const void *src, const void *g, float *slabs, int batch, int side, int cin, int cout, int *splits,
-                           hipStream_t st);
-
 // posgemm.hip (internal): the 4^3 -> 2^3 convolution written as float32 split-K slabs only, in the MFMA FRAGMENT order of the
 // producing workgroup (no transpose on the producer's side).  Piece of (position p, share s, sample tile mt, channel tile nt) =
 // ws + (((first[p] + s) * mtiles + mt) * ntn + nt) * 256 * 128 floats; inside a piece the f32x4 holding channels c .. c + 3 (c % 4 == 0,

@@ -263,7 +263,7 @@ __global__ __launch_bounds__(512, 1) void ctw_kernel(const __bf16 *__restrict__ 
                                                            *reinterpret_cast<const bf16x8 *>(&F[CT]), acc[COT][CT], 0, 0, 0)
 
 // STATS (round 4, the training step's forward pass): also leaves the per-workgroup column sums (sum, sum of squares per output channel, of the
-// bf16 values it stores) as partial[(workgroup * 2 + {0, 1}) * 64 + channel] -- the layout of bn_reduce_kernel's partials, so
+// bf16 values it stores) as partial[(workgroup * 2 + {0, 1}) * 64 + channel] -- the layout of bn_reduce_kernel's partials (bn.hip), so
 // vv_bn_finalize_stats turns them into the batch statistics and the 134 MB statistics sweep over this layer's output is not run.
 template <int ACT, bool STATS = false>
 __global__ __launch_bounds__(512, 1) void ctw16_kernel(const __bf16 *__restrict__ x, const __bf16 *__restrict__ w,

@@ -3,7 +3,7 @@
 //   dW[t][ci][co] = sum over (b, o) of src[b, 2o - 1 + t, ci] * g[b, o, co]          (zero outside the grid)
 //
 // (src = layer input and g = dL/d(conv out) for a Conv3D -> Keras [4,4,4,cin,cout]; src = dL/d(out) and g = layer input
-// for a Conv3DTranspose -> Keras [4,4,4,cout_T,cin_T].)  The reduction-GEMM form in train.hip streams the 64-tap im2col row
+// for a Conv3DTranspose -> Keras [4,4,4,cout_T,cin_T].)  The reduction-GEMM form in wgrad.hip streams the 64-tap im2col row
 // of every output position through LDS: 1/32 byte per MAC at its 128 x 128 tile, and the L2 -> LDS path is what bounds it
 // (0.19 ms on the 64 -> 128 layer at batch 256, against 0.11 ms for the forward convolution of the same size).  Here the
 // taps are split by the parity of 2o - 1 + t per axis (t = 2a + r): for one parity r the sources of all output positions
@@ -16,10 +16,11 @@
 // the boxes.  A box is 128 consecutive output rows (b, od, oh, ow): 16 x 8 of one depth plane (S = 16), two planes (S = 8)
 // or two whole samples (S = 4).  Both operands are k-strided (k = output position), so the LDS images stay row-major as
 // staged by LDS-DMA -- [32-channel block][row][64 B] -- and the fragments come out of ds_read_b64_tr_b16 (see
-// wgrad_bf16_kernel in train.hip for the lane mapping); every lane supplies its own row address, which is what lets the
+// wgrad_bf16_kernel in wgrad.hip for the lane mapping); every lane supplies its own row address, which is what lets the
 // eight taps read the same tile at different cell offsets.  Two stages (<= 72 KB each): the DMA of box i+1 runs under the
-// 64 MFMAs per wave of box i.  Partial panels go to per-split slabs, summed in split order by train.hip's reduce kernel.
-#include "common.h"
+// 64 MFMAs per wave of box i.  Partial panels go to per-split slabs, summed in split order by wgrad.hip's reduce
+// (vv_wgrad_reduce_launch).  Whether this form runs, and its split over the boxes, is wgrad_plan.h's decision (WG_PHASE, wg_phase_plan).
+#include "wgrad.h"
 
 namespace {
 
@@ -232,18 +233,6 @@ __global__ __launch_bounds__(512, 1) void wgrad_phase_kernel(const WgPhaseArgs a
         }
 }
 
-struct WgPhasePlan { int nboxes, splits, bps; };
-WgPhasePlan wg_phase_plan(long rows, int cin, int cout) {
-    WgPhasePlan p;
-    p.nboxes = (int)((rows + 127) / 128);
-    const int kinds = 8 * (cin / 64) * (cout / 128);
-    int splits = 1;
-    while (kinds * splits * 2 <= 256 && splits * 2 <= p.nboxes) splits *= 2;     // one workgroup per CU (LDS-bound occupancy)
-    p.bps = (p.nboxes + splits - 1) / splits;
-    p.splits = (p.nboxes + p.bps - 1) / p.bps;
-    return p;
-}
-
 template <int LS>
 void wg_phase_launch(const WgPhaseArgs &a, int kinds, hipStream_t st) {
     using G = WgGeo<LS>;
@@ -253,32 +242,15 @@ void wg_phase_launch(const WgPhaseArgs &a, int kinds, hipStream_t st) {
 
 }  // namespace
 
-bool vv_wgrad_phase_ok(const void *src, const void *g, int batch, int side, int cin, int cout) {
-    if (vv_hook("VV_NO_WGRAD_PHASE") || vv_hook("VV_WGRAD_F32")) return false;
-    const int S = side / 2;
-    if (S != 4 && S != 8 && S != 16) return false;
-    if (cin % 64 || cout % 128) return false;
-    if ((size_t)batch * side * side * side * cin * 2 >= 0xFFFFFFF0ull || (size_t)batch * S * S * S * cout * 2 >= 0xFFFFFFF0ull) return false;
-    if ((long)batch * S * S * S < 128 * 8) return false;          // tiny problems: the reduction-GEMM form splits finer
-    return vv_aligned16(src) && vv_aligned16(g);
-}
-
-// Slab bytes for `rows` output positions (the plan depends on the row count and the channel blocks only).
-size_t vv_wgrad_phase_ws(long rows, int cin, int cout) {
-    if (cin <= 0 || cout <= 0 || cin % 64 || cout % 128) return 0;
-    return (size_t)wg_phase_plan(rows, cin, cout).splits * 64 * cin * cout * sizeof(float);
-}
-
-// Launches the phase kernel; the caller sums the *splits slabs [64 cin][cout].
-void vv_wgrad_phase_launch(const void *src, const void *g, float *slabs, int batch, int side, int cin, int cout, int *splits,
+// Launches the phase kernel on plan `p` (wg_phase_plan of these shapes); the caller sums the p.splits slabs [64 cin][cout].
+void vv_wgrad_phase_launch(const void *src, const void *g, float *slabs, int batch, int side, int cin, int cout, const WgradPlan &p,
                            hipStream_t st) {
     const int S = side / 2;
-    const WgPhasePlan p = wg_phase_plan((long)batch * S * S * S, cin, cout);
-    WgPhaseArgs a{src, g, slabs, (long)batch * S * S * S, batch, vv_log2(side), cin, cout, p.nboxes, p.bps, p.splits,
+    const long rows = (long)batch * S * S * S;
+    WgPhaseArgs a{src, g, slabs, rows, batch, vv_log2(side), cin, cout, (int)((rows + 127) / 128), p.rps, p.splits,
                   (unsigned)((size_t)batch * side * side * side * cin * 2), (unsigned)((size_t)batch * S * S * S * cout * 2)};
     const int kinds = 8 * (cin / 64) * (cout / 128);
     if (S == 16) wg_phase_launch<4>(a, kinds, st);
     else if (S == 8) wg_phase_launch<3>(a, kinds, st);
     else wg_phase_launch<2>(a, kinds, st);
-    *splits = p.splits;
 }

@@ -2,6 +2,7 @@
 achieved bytes/s against the 6.29 TB/s copy rate.  Optional hooks (hook build only): VV_BN_NB = block cap of the two reductions,
 VV_BN_SWEEP = block cap of the two element-wise sweeps.  python profiles/microbench/mb_bn.py [tag]"""
 import ctypes, json, os, sys
+os.environ.setdefault('VOXVAE_TEST_HOOKS', '1')   # the kernel-form overrides live in lib/libvoxvae_hooks.so (voxvae/lib.py)
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'anytime-3d-reconstruction_amd'))
 import torch
@@ -34,4 +35,5 @@ for name, R, C in shapes:
         e1.record(); torch.cuda.synchronize()
         us = e0.elapsed_time(e1) / 50 * 1e3
         res['%s [%d x %d] %s' % (name, R, C, label)] = {'us': round(us, 2), 'TBps': round(moved / us / 1e6, 3)}
-print(json.dumps({'hooks': {k: os.environ.get(k) for k in ('VV_BN_NB', 'VV_BN_SWEEP', 'VV_BN_ROWS')}, 'results': res}, indent=1))
+print(json.dumps({'hooks': {k: os.environ.get(k) for k in ('VV_BN_NB', 'VV_BN_SWEEP', 'VV_BN_ROWS')}, 'hooks_requested': L.hooks_requested(),
+                  'results': res}, indent=1))

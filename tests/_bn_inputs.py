@@ -1,7 +1,7 @@
 """Inputs, float64 references and error bounds of the BatchNorm training-op tests (tests/test_gpu_train_ops.py; host self-test:
 tests/test_tol_host.py).  No GPU.
 
-Everything the kernels of csrc/train.hip read is an integer or a power of two here, so that most of what they compute is exact in
+Everything the kernels of csrc/bn.hip read is an integer or a power of two here, so that most of what they compute is exact in
 float32 and the rest has an error that can be counted operation by operation:
 
   x       integers -4..4 plus a per-channel integer offset -2..2 (|x| <= 6: exact in bf16), sum x^2 < 2^24 at every shape

@@ -7,9 +7,10 @@ accumulators of both MFMA paths, the per-split slabs and either reduce kernel th
 the summation order: the stored result must EQUAL the float64 definition.  There is no zero among the values, so a dropped,
 doubled or misplaced product always changes the sum.
 
-The split arithmetic of csrc/train.hip and csrc/wgrad_phase.hip is restated below (wgrad_plan, wgrad_plan_bf16, wg_phase_plan and the
+The split arithmetic and the routes of csrc/wgrad_plan.h are restated below (wgrad_plan, wgrad_plan_bf16, wg_phase_plan and the
 choice of reduce kernel) for ONE purpose: tests/test_gpu_wgrad_exact.py asserts with it that the tables still hold a case without a
-reduce pass, one of the plain reduce, one of the sliced reduce and a phase plan of several splits.  Nothing is computed from it."""
+reduce pass, one of the plain reduce, one of the sliced reduce and a phase plan of several splits.  Nothing is computed from it.
+tests/test_wgrad_plan_host.py holds it against the header itself, case by case."""
 import functools
 
 import numpy as np
@@ -41,18 +42,18 @@ def wgrad_conv_ref(src, g):
 DENSE_CASES = [
     (300, 160, 96, 160, 'f32', 'f32'),      # wgrad_kernel<0, 64> (n % 128 != 0): ragged M tile (160 = 2 * 64 + 32), ragged N tile (96 = 64 + 32), r < r_end inside a 32-row chunk
     (64, 128, 4096, 128, 'f32', 'f32'),     # wgrad_kernel<0, 128>: wgrad_plan's bn = 128 (n % 128 == 0)
-    (1000, 32, 32, 32, 'f32', 'f32'),       # 32 splits, m * n = 1024: launch_wgrad_reduce's `splits >= 16 && n <= 65536` -> wgrad_reduce_sliced_kernel
+    (1000, 32, 32, 32, 'f32', 'f32'),       # 32 splits, m * n = 1024: wgrad_reduce_sliced's `splits >= 16 && n <= 65536` -> wgrad_reduce_sliced_kernel
     (300, 160, 96, 192, 'f32', 'f32'),      # lda != m: `r * a.lda + m` of wgrad_kernel<0>; the 32 floats behind every row hold 3
     (300, 160, 96, 192, 'bf16', 'bf16'),    # lda != m: `(r * a.lda + mcol + pch * 8) * 2` of wgrad_bf16_kernel<0>, a_bytes = rows * lda * 2
     (37, 160, 96, 160, 'bf16', 'bf16'),     # one 64-row chunk: wgrad_plan_bf16 splits == 1, launch_wgrad_bf16 `a.slabs = out` (no reduce pass)
     (1000, 160, 96, 160, 'bf16', 'bf16'),   # wgrad_bf16_kernel<0>: 16 splits, M = 160 and N = 96 ragged against the 128 x 128 tile
-    (300, 36, 20, 36, 'bf16', 'bf16'),      # wgrad_bf16_ok `M % 32 || N % 32`: bf16 operands widened by wgrad_kernel<0, 64> (ld4_rt)
-    (300, 160, 96, 160, 'bf16', 'f32'),     # vv_wgrad_dense `a_dtype == VV_BF16 && g_dtype == VV_BF16` fails: a_bf16 = 1, g_bf16 = 0
+    (300, 36, 20, 36, 'bf16', 'bf16'),      # wgrad_dense_route `m % 32 == 0 && n % 32 == 0` fails: bf16 operands widened by wgrad_kernel<0, 64> (ld4_rt)
+    (300, 160, 96, 160, 'bf16', 'f32'),     # wgrad_dense_route `a_dtype == WG_DT_BF16 && g_dtype == WG_DT_BF16` fails: a_bf16 = 1, g_bf16 = 0
     (300, 160, 96, 160, 'f32', 'bf16'),     # the other order: a_bf16 = 0, g_bf16 = 1
 ]
 # vv_wgrad_conv_k4s2, reduction-GEMM forms: (B, side, cin, cout, src dtype, g dtype)
 CONV_CASES = [
-    (3, 8, 64, 128, 'f32', 'f32'),          # cin = 64: a 128-column tile spans two taps (`t = mcol / a.cin`); 192 rows < 128 * 8, so vv_wgrad_phase_ok says no
+    (3, 8, 64, 128, 'f32', 'f32'),          # cin = 64: a 128-column tile spans two taps (`t = mcol / a.cin`); 192 rows < 128 * 8, so wgrad_conv_route leaves the phase form out
     (3, 8, 64, 128, 'bf16', 'bf16'),        # wgrad_bf16_kernel<1>
     (3, 8, 64, 128, 'bf16', 'f32'),         # mixed: wgrad_kernel<1, 128> with a_bf16 = 1
     (5, 8, 64, 32, 'f32', 'f32'),           # cout % 128 != 0: wgrad_kernel<1, 64>, `nn < a.N`
@@ -62,7 +63,7 @@ CONV_CASES = [
     (5, 2, 64, 64, 'f32', 'f32'),           # side == 2: din_log2 == 1, lo == 0, omsk == 0, r == b; per axis taps 0 and 3 are padding
     (5, 2, 64, 64, 'bf16', 'bf16'),         # side == 2 on wgrad_bf16_kernel<1>; 5 rows: splits == 1, written without a reduce pass
     (3, 16, 1, 64, 'f32', 'f32'),           # one source channel: wgrad_kernel<2, 64>; 24 splits, 4096 outputs: the sliced reduce
-    (3, 16, 1, 64, 'f32', 'bf16'),          # `cin == 1 && side >= 4 && g_dtype == VV_BF16`: launch_wgrad_bf16<2>, `a.N <= 64` -> wgrad_bf16_kernel<2, true>
+    (3, 16, 1, 64, 'f32', 'bf16'),          # `cin == 1 && side >= 4` with bf16 g (WG_BF16_GRID): launch_wgrad_bf16<2>, wgrad_grid_one_tile -> wgrad_bf16_kernel<2, true>
     (2, 8, 1, 128, 'f32', 'bf16'),          # cout > 64: wgrad_bf16_kernel<2, false>, column blocks 2, 3 of A zeroed once
     (2, 2, 1, 32, 'f32', 'f32'),            # side == 2 with one channel: wgrad_kernel<2, 64>
     (2, 2, 1, 32, 'f32', 'bf16'),           # `side >= 4` fails: bf16 g stays on wgrad_kernel<2, 64> (g_bf16 = 1)
@@ -136,7 +137,7 @@ def _cdiv(a, b):
 
 
 def wgrad_plan(R, M, N):
-    """train.hip wgrad_plan -> (bn, splits): 64 x bn tiles, 32-row chunks."""
+    """wgrad_plan.h wgrad_plan -> (bn, splits): 64 x bn tiles, 32-row chunks."""
     bn = 128 if N % 128 == 0 else 64
     tiles, chunks, splits = _cdiv(M, 64) * _cdiv(N, bn), _cdiv(R, 32), 1
     while tiles * splits < 1024 and splits * 2 <= chunks and splits < 256:
@@ -145,7 +146,7 @@ def wgrad_plan(R, M, N):
 
 
 def wgrad_plan_bf16(R, M, N):
-    """train.hip wgrad_plan_bf16 -> splits: 128 x 128 tiles, 64-row chunks."""
+    """wgrad_plan.h wgrad_plan_bf16 -> splits: 128 x 128 tiles, 64-row chunks."""
     tiles, chunks, splits = _cdiv(M, 128) * _cdiv(N, 128), _cdiv(R, 64), 1
     want = 1024 if tiles <= 2 else 512
     while tiles * splits < want and splits * 2 <= chunks and splits < want:
@@ -154,7 +155,7 @@ def wgrad_plan_bf16(R, M, N):
 
 
 def wg_phase_plan(rows, cin, cout):
-    """wgrad_phase.hip wg_phase_plan -> splits: boxes of 128 rows."""
+    """wgrad_plan.h wg_phase_plan -> splits: boxes of 128 rows."""
     nboxes, kinds, splits = _cdiv(rows, 128), 8 * (cin // 64) * (cout // 128), 1
     while kinds * splits * 2 <= 256 and splits * 2 <= nboxes:
         splits *= 2
@@ -162,16 +163,22 @@ def wg_phase_plan(rows, cin, cout):
 
 
 def reduce_kind(splits, n, bf16_kernel):
-    """launch_wgrad_reduce's choice; the bf16 kernel alone writes dw itself when there is one split (launch_wgrad_bf16)."""
+    """wgrad_reduce_kind's choice; the bf16 kernel alone writes dw itself when there is one split (launch_wgrad_bf16)."""
     if bf16_kernel and splits == 1:
         return 'none'
     return 'sliced' if splits >= 16 and n <= 65536 else 'plain'
 
 
-def dense_route(case):
-    """-> (kernel, splits, reduce) of vv_wgrad_dense without overrides (aligned operands)."""
+def _span_ok(elems):
+    """A bf16 operand of `elems` elements ends below the 32-bit buffer offset the bf16 kernels keep for "out of range"."""
+    return elems * 2 < 0xFFFFFFF0
+
+
+def dense_route(case, env=()):
+    """-> (kernel, splits, reduce) of vv_wgrad_dense under the overrides `env` (aligned operands)."""
     rows, m, n, lda, adt, gdt = case
-    if adt == gdt == 'bf16' and m % 32 == 0 and n % 32 == 0 and lda % 8 == 0:
+    if (adt == gdt == 'bf16' and 'VV_WGRAD_F32' not in env and m % 32 == 0 and n % 32 == 0 and lda % 8 == 0
+            and _span_ok(rows * lda) and _span_ok(rows * n)):
         s = wgrad_plan_bf16(rows, m, n)
         return 'bf16', s, reduce_kind(s, m * n, True)
     s = wgrad_plan(rows, m, n)[1]
@@ -183,14 +190,15 @@ def conv_route(case, env=()):
     B, side, cin, cout, sdt, gdt = case
     rows, m = conv_rows(case), 64 * cin
     f32_only = 'VV_WGRAD_F32' in env
-    if cin != 1 and sdt == gdt == 'bf16' and not f32_only:
+    g_fits = _span_ok(rows * cout)
+    if cin != 1 and sdt == gdt == 'bf16' and not f32_only and g_fits and _span_ok(B * side ** 3 * cin):
         if 'VV_NO_WGRAD_PHASE' not in env and side // 2 in (4, 8, 16) and cout % 128 == 0 and rows >= 1024:
             s = wg_phase_plan(rows, cin, cout)
             return 'phase', s, reduce_kind(s, m * cout, False)
         if cout % 32 == 0:
             s = wgrad_plan_bf16(rows, m, cout)
             return 'bf16', s, reduce_kind(s, m * cout, True)
-    if cin == 1 and side >= 4 and gdt == 'bf16' and cout % 32 == 0 and not f32_only:
+    if cin == 1 and side >= 4 and gdt == 'bf16' and cout % 32 == 0 and not f32_only and g_fits:
         s = wgrad_plan_bf16(rows, 64, cout)
         return 'bf16 one channel, %s' % ('one tile' if cout <= 64 else 'full tile'), s, reduce_kind(s, 64 * cout, True)
     s = wgrad_plan(rows, m, cout)[1]

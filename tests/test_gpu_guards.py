@@ -173,7 +173,7 @@ row(GA.test_encoder_final_pool_max, 'dtype,D', ('bf16', 32), ['vv_pack_conv_k4s1
 row(GA.test_bit_packed_device_data_path, '', (), ['vv_pack_bits', 'vv_unpack_bits_gather'], '5 x 4096 voxels packed, 3 rows gathered out of order')
 
 # ----------------------------------------------------------------------------------------------------------------- training ops
-# train.hip statistics / wgrad kernels cut the rows into blocks (BR = 32 / 64 rows a chunk) whose partials land in the workspace
+# bn.hip statistics / wgrad.hip kernels cut the rows into blocks (BR = 32 / 64 rows a chunk) whose partials land in the workspace
 for dt in ('f32', 'bf16'):
     row(O.test_batchnorm_train_ops, 'rows,C', (777, 128), ['vv_bn_train_stats', 'vv_bn_act_fwd', 'vv_bn_act_bwd'], 'rows = 777: odd against every row block', dtname=dt)
     row(O.test_batchnorm_train_ops, 'rows,C', (5, 256), ['vv_bn_train_stats', 'vv_bn_act_fwd', 'vv_bn_act_bwd'], 'rows = 5: fewer rows than a block', dtname=dt)

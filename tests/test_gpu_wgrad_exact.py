@@ -1,4 +1,4 @@
-"""Exact GPU tests of the weight-gradient entries vv_wgrad_dense and vv_wgrad_conv_k4s2 (csrc/train.hip, csrc/wgrad_phase.hip).
+"""Exact GPU tests of the weight-gradient entries vv_wgrad_dense and vv_wgrad_conv_k4s2 (csrc/wgrad.hip, csrc/wgrad_phase.hip).
 
 Operands are non-zero integers of magnitude 1..4 (tests/_wgrad_inputs.py): exact in float32 and bf16, integer products, every partial
 sum below 2^24.  The float32 accumulators of both MFMA paths, the per-split slabs and either reduce kernel then give ONE answer in any

@@ -251,7 +251,8 @@ def _nonzero_small_ints(a):
 def test_wgrad_case_tables_reach_every_reduce_form():
     """The dispatch as restated in tests/_wgrad_inputs.py: the tables hold a case that writes dw without a reduce pass, one of the plain
     reduce, one of the sliced reduce (on either kernel) and phase plans of several splits, and every kernel form they name.  If the
-    split arithmetic of train.hip changes under the tables, this says so instead of the GPU tests silently testing less."""
+    split arithmetic of wgrad_plan.h changes under the tables, this says so instead of the GPU tests silently testing less
+    (tests/test_wgrad_plan_host.py holds the restatement against the header)."""
     routes = [WI.dense_route(c) for c in WI.DENSE_CASES] + [WI.conv_route(c) for c in WI.CONV_CASES]
     phase = [WI.conv_route(c + ('bf16', 'bf16'), env) for c in WI.PHASE_CASES for env in WI.PHASE_ENVS]
     print('\n' + '\n'.join('%-40s %s' % (c, r) for c, r in zip(WI.DENSE_CASES + WI.CONV_CASES, routes)))
