@@ -16,6 +16,17 @@ from voxvae import synthetic as syn
 CLASSES = 12
 
 
+def _kmeans_aei(euler, k, max_iter, **kw):
+    """reference pascal3D.py:156-181: the rows (sin a, sin e, sin i, cos a, cos e, cos i) in float64 of every object's Euler angles, in
+    storage order, clustered by function.kmeans_cosine(...).kmeansSample() -> (centres [k,6], xtoc [n], distance [n]) as numpy."""
+    from src.module.function import kmeans_cosine
+    if k is None:
+        raise ValueError('getKmeansAEI needs k (the reference calls it with k = 30 * 12)')
+    e = np.asarray(euler, dtype=np.float64).reshape(-1, 3)
+    AEI = np.concatenate([np.sin(e), np.cos(e)], axis=1)
+    return kmeans_cosine(X=AEI, k=k, max_iter=max_iter, **kw).kmeansSample()
+
+
 class dataLoaderSingleObject(object):
     def __init__(self, trainOrVal='train', Pascal3DDataPath=None, voxel=64, instances=None):
         n = 256 if trainOrVal == 'train' else 96
@@ -71,6 +82,10 @@ class dataLoaderSingleObject(object):
         inst = np.zeros((len(idx), 1), dtype='float32') if self._insts is None else np.eye(int(self._instances), dtype='float32')[self._insts[idx]]
         e = self._euler[idx]
         return inst, cls, np.sin(e), np.cos(e), imgs.astype('float32'), out.astype('float32')
+
+    def getKmeansAEI(self, k=None, max_iter=1000, **kw):
+        """reference :156-181 over the loader's objects in storage order; `device=` / `host=` go to kmeans_cosine."""
+        return _kmeans_aei(self._euler, k, max_iter, **kw)
 
 
 class deviceDataLoaderSingleObject(object):
@@ -183,6 +198,7 @@ class deviceDataLoaderSingleObject(object):
         self._cls = torch.from_numpy(np.eye(CLASSES, dtype='float32')[classes]).to(dev)
         self._inst = torch.from_numpy(np.zeros((n, 1), dtype='float32') if insts is None else np.eye(int(instances), dtype='float32')[insts]).to(dev)
         self._sin, self._cos = torch.from_numpy(np.sin(euler)).to(dev), torch.from_numpy(np.cos(euler)).to(dev)
+        self._euler = euler                                                  # host copy, storage order: getKmeansAEI
         self._gen = torch.Generator(device=dev)
         if seed is not None:
             self._gen.manual_seed(int(seed))
@@ -221,6 +237,12 @@ class deviceDataLoaderSingleObject(object):
         flipped = (params[:, A.P_FLIP] & 1) != 0
         sin[:, 0] = torch.where(flipped, -sin[:, 0], sin[:, 0])              # azimuth -> -azimuth: the sine changes sign, the cosine does not
         return self._inst[idx], self._cls[idx], sin, self._cos[idx], images, out
+
+    def getKmeansAEI(self, k=None, max_iter=1000, **kw):
+        """As dataLoaderSingleObject.getKmeansAEI, on this loader's device unless `device=` / `host=` say otherwise."""
+        if 'device' not in kw and 'host' not in kw:
+            kw['device'] = self._device
+        return _kmeans_aei(self._euler, k, max_iter, **kw)
 
 
 # what the entry scripts' --loader names

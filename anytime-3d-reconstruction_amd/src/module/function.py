@@ -85,3 +85,47 @@ def voxelPrecisionRecallCurve(xTarget, xPred, probs, inclusive=True):
     curve.update(xTarget, p, group=torch.arange(B, dtype=torch.int32, device=p.device))
     tp, fp, fn, _, _ = curve.counts_device()
     return DeviceArray(tp.float()), DeviceArray(fp.float()), DeviceArray(fn.float())
+
+
+class kmeans_cosine(object):
+    """reference function.py:156-200: k-means over rows (sin a, sin e, sin i, cos a, cos e, cos i) with its "cosine" distance, on
+    vv_kmeans_cosine (voxvae/kmeans.py; csrc/kmeans_cosine.h states the arithmetic).  Same constructor, `_kmeans` and `kmeansSample`,
+    same numpy results; the picks of kmeansSample come from Python's `random` in the reference's order, so `random.seed(s)` reproduces
+    them.  `host=True` runs the same code compiled for the CPU, `device=` names the GPU; by default the device when there is one.
+    `iterations` holds how many iterations of the last `_kmeans` did work (the rest would have repeated the last one bit for bit)."""
+
+    def __init__(self, X, k, max_iter=100, device=None, host=None):
+        self._X = np.array(X, dtype=np.float64)
+        self._k = k
+        self._max_iter = max_iter
+        self._host = (not torch.cuda.is_available()) if host is None and device is None else bool(host)
+        self._device = device
+        self.iterations = 0
+
+    def _kmeans(self, X, centres, max_iter=100):
+        """-> (centres [k,6] float64, xtoc [N] int64, distance [N] float64); a float64 numpy `centres` is updated in place, as the
+        reference updates it.  max_iter=0 -> (centres, None, None)."""
+        from voxvae import kmeans as _K
+        if max_iter < 1:
+            return centres, None, None
+        x, c = np.asarray(X, dtype=np.float64), np.asarray(centres, dtype=np.float64)
+        if not self._host and self._device is not None:
+            x, c = torch.from_numpy(np.ascontiguousarray(x)).to(self._device), torch.from_numpy(np.ascontiguousarray(c)).to(self._device)
+        out, xtoc, dist, self.iterations = _K.kmeans(x, c, max_iter, host=self._host)
+        out = out.cpu().numpy()
+        if isinstance(centres, np.ndarray) and centres.dtype == np.float64 and centres.shape == out.shape:
+            centres[...] = out
+            out = centres
+        return out, xtoc.cpu().numpy().astype(np.int64), dist.cpu().numpy()
+
+    def kmeansSample(self, nsample=0, *, _sample_idx=None, _centre_idx=None):
+        """reference :193-200: 10 iterations on a random sample of rows from k random rows of X, then max_iter iterations on all of X.
+        `_sample_idx` / `_centre_idx` (extensions) inject the two picks."""
+        import random
+        N = self._X.shape[0]
+        if nsample == 0:
+            nsample = max(2 * np.sqrt(N), 10 * self._k)
+        sample = random.sample(range(N), int(nsample)) if _sample_idx is None else list(_sample_idx)
+        first = random.sample(range(N), int(self._k)) if _centre_idx is None else list(_centre_idx)
+        centres = self._kmeans(self._X[sample], self._X[first], max_iter=10)[0]
+        return self._kmeans(self._X, centres, max_iter=self._max_iter)

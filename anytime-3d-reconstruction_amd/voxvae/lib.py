@@ -179,6 +179,11 @@ SIGNATURES = {
     'vv_augment_colour_workspace_bytes': (_sz, [_i, _i, _i]),
     'vv_augment_images_ex': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _i, _vp]),
     'vv_augment_images_ex_host': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _i]),
+    'vv_kmeans_cosine_workspace_bytes': (_sz, [_i, _i]),
+    'vv_kmeans_cosine': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'vv_kmeans_cosine_host': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    'vv_kmeans_cosine_assign': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
+    'vv_kmeans_cosine_assign_host': (_i, [_vp, _i, _vp, _i, _vp, _vp]),
 }
 
 

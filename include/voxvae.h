@@ -850,6 +850,31 @@ int vv_augment_images_ex_host(const unsigned char *images, const long long *imag
                               int out_rows, int out_cols, float *out, const int *colour, void *workspace, size_t workspace_bytes,
                               int max_rows, int max_cols);
 
+/* ---- Viewpoint clustering (csrc/kmeans_cosine.h states every expression, the tie rule and the summation order): the reference's
+ * kmeans_cosine._kmeans, src/module/function.py:166-191.  All arithmetic is IEEE float64.
+ *   x          float64 [n][6] = (sin a, sin e, sin i, cos a, cos e, cos i) per point
+ *   centres    float64 [k][6], in-out: the initial centres on entry, the centres after the last update on return
+ *   xtoc       int32 [n]: the nearest centre of every point, the LOWEST index among equals (np.argmin's rule)
+ *   distance   float64 [n]: the distance to that centre.  Both are the last iteration's assignment, taken before its update
+ *   iterations int32 [1]: the iterations that did work.  An iteration that changes no label makes every later one a repetition, bit
+ *              for bit; those are not run (host) or return at their first instruction (device), and the result is that of max_iter
+ *              full iterations
+ *   workspace  vv_kmeans_cosine_workspace_bytes(n, k) bytes (pure host arithmetic; 0 for arguments out of range), 8-byte aligned.
+ *              Written before it is read; the result does not depend on its contents or on workspace_bytes beyond that minimum.
+ * vv_kmeans_cosine: every pointer a device pointer; 2 * max_iter launches on `hip_stream`, enqueued by this one call with no read-back
+ *   in between (per iteration: a workgroup per 256 points with the centres in LDS, then the chunk-order reduction).  No atomics: the
+ *   same bits on every run, and the bits of the host entry.
+ * vv_kmeans_cosine_host: the same code on host pointers, no stream, no workspace; needs no GPU.
+ * vv_kmeans_cosine_assign / _assign_host: xtoc (and distance, unless NULL) of points against given centres; one launch.
+ * Refused before any launch: a NULL required pointer (VV_ERR_NULL); n < 1, n > 1048576, k < 1, k > 1024, max_iter < 1 or
+ *   max_iter > 65536 (VV_ERR_SHAPE); a pointer below its element's alignment (VV_ERR_ALIGN); a short workspace (VV_ERR_WORKSPACE). */
+size_t vv_kmeans_cosine_workspace_bytes(int n, int k);
+int vv_kmeans_cosine(const double *x, int n, double *centres, int k, int max_iter, int *xtoc, double *distance, int *iterations,
+                     void *workspace, size_t workspace_bytes, void *hip_stream);
+int vv_kmeans_cosine_host(const double *x, int n, double *centres, int k, int max_iter, int *xtoc, double *distance, int *iterations);
+int vv_kmeans_cosine_assign(const double *x, int n, const double *centres, int k, int *xtoc, double *distance, void *hip_stream);
+int vv_kmeans_cosine_assign_host(const double *x, int n, const double *centres, int k, int *xtoc, double *distance);
+
 #ifdef __cplusplus
 }
 #endif
